@@ -23,11 +23,20 @@ time is the max over ranks.
 `--gpus N` without torchrun: the parent spawns N rank processes (RANK / LOCAL_RANK / WORLD_SIZE /
 MASTER_*) before any GPU call and relays rank 0's line.  Under torchrun each process is one rank.
 
-Prints ONE JSON line (rank 0) with value = Msamples/s of the whole job, a `roofline` object for the
-dominant pass (algorithmic bytes per launch / its average HIP-event duration over the timed steps) and a `cpu_baseline` object (the C restatement of
-vectorwave-core's scalar loops, timed on a bounded sample on this host's cores, N = 1 only).
+Prints ONE JSON line (rank 0) with value = Msamples/s of the whole job and `ms_per_step`, the
+milliseconds one timed step took.  A plain run does only that: set up, settle, warm up, time the K steps,
+print.  `--dump-outputs DIR` also writes what the last timed step computed (a fixed sample of rows) as
+DIR/<name>.npy.
+
+`--full` adds everything else, each in a run of its own after the timed region: the correctness guard on
+the timed buffers (rows against the C restatement of vectorwave-core, perfect reconstruction), a
+`roofline` object for the dominant pass (algorithmic bytes per launch / its average HIP-event duration
+over the timed steps; a one-context timing where the headline's launches overlap), the isolated per-pass
+timing, the other accumulation mode, weak scaling (N > 1) and a `cpu_baseline` object (the restatement's
+scalar loops, timed on a bounded sample on this host's cores, N = 1 only).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--config db4|sym8-denoise|db8-stream|coif5-f32]
+                    [--dump-outputs DIR] [--full]
 """
 import argparse
 import json
@@ -96,6 +105,13 @@ def parse(argv=None):
     p.add_argument("--warmup", type=int, default=50)
     p.add_argument("--settle", type=float, default=1.0, help="seconds of untimed steps before warmup (clock settle)")
     p.add_argument("--config", default="db4", choices=sorted(CONFIGS))
+    p.add_argument("--full", action="store_true",
+                   help="after the timed steps also run the correctness guard, the roofline's one-context and "
+                        "isolated kernel timings, the other accumulation mode, weak scaling (N > 1) and the CPU "
+                        "baseline (the --no-* switches below trim these)")
+    p.add_argument("--dump-outputs", default="", metavar="DIR",
+                   help="write what the last timed step computed as DIR/<name>.npy: a fixed, seeded sample of rows "
+                        "of every array a caller of the timed path receives (see dump_outputs())")
     p.add_argument("--batch", type=int, default=0, help="override the GLOBAL batch")
     p.add_argument("--wavelet", default="", help="override the config's wavelet (experiments)")
     p.add_argument("--exact", action="store_true",
@@ -762,8 +778,10 @@ def run(args, world, rank, local):
     elapsed = max_over_ranks(torch, dist, world, elapsed, dev)
     host_elapsed = max_over_ranks(torch, dist, world, host_elapsed, dev)
     value = Bg * N * args.steps / elapsed / 1e6
-    # correctness guard on the timed buffers (outside the timed region): fails the run loudly
-    check = verify(torch, wl, w, J, pipeline, flags, nat)
+    # --full: correctness guard on the timed buffers (outside the timed region): fails the run loudly
+    check = verify(torch, wl, w, J, pipeline, flags, nat) if args.full else None
+    # the timed buffers still hold the last timed step's results here: nothing has run since
+    dumped = dump_outputs(torch, wl, args.dump_outputs, Bg, start, world, rank) if args.dump_outputs else None
     checks = [None] * world
     if world > 1:
         dist.all_gather_object(checks, check)
@@ -781,7 +799,7 @@ def run(args, world, rank, local):
     # timed once more by ONE context over the same rows (after the headline's timed region, same
     # graph method).  With K = 1 the headline's own launches are used.
     kfams, ksampled, kpass_ms = fams, sampled, pass_ms
-    if (K > 1 or overlap) and events:
+    if args.full and (K > 1 or overlap) and events:
         wk1 = Workload(engines[:1], streams[:1], w, J, rows, N, dtype, pipeline, start, torch, *rot)
         _, _, kfams, ksampled, kpass_ms = measure(torch, dist, world, wk1, flags, args.launch, args.steps,
                                                   args.warmup, min(args.settle, 0.5), events)
@@ -792,7 +810,7 @@ def run(args, world, rank, local):
     # of the forward's coefficient rows (sc1 stores) that drains while it runs.  Reported beside the roofline,
     # not in place of it.
     iso = None
-    if events and pipeline == "fwd+inv" and not args.no_isolated:
+    if args.full and events and pipeline == "fwd+inv" and not args.no_isolated:
         wki = Workload(engines[:1], streams[:1], w, J, rows, N, dtype, pipeline, start, torch, *rot)
         prime = wki.parts[0].step_fn(flags)
         with torch.cuda.stream(wki.parts[0].stream):
@@ -863,7 +881,7 @@ def run(args, world, rank, local):
 
     # ---- the other accumulation mode, same rows, timed the same way (beside the headline)
     alt = None
-    if not args.no_alt:
+    if args.full and not args.no_alt:
         aflags = flags ^ nat.FLAG_FMA
         (ael, _), _, afams, asampled, _ = measure(torch, dist, world, wl, aflags, args.launch, args.steps,
                                                   args.warmup, min(args.settle, 0.3), events)
@@ -877,7 +895,7 @@ def run(args, world, rank, local):
 
     # ---- weak scaling (N > 1): every rank owns a full per-GPU batch of Bg rows (the N = 1 workload)
     weak = None
-    if world > 1 and not args.no_weak:
+    if args.full and world > 1 and not args.no_weak:
         # the full per-GPU batch gets its own schedule, buffer sets and contexts (reusing the
         # shard's R and overlap decision allocated 32 rotated 4096 x 4096 sets and overlapped 4096 rows)
         Kw, overlap_w, rot_w = plan_schedule(args, Bg, N, esz, cus, pipeline)
@@ -896,7 +914,7 @@ def run(args, world, rank, local):
     close_engines(engines, ov)
 
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         cpu = cpu_baseline(w, J, N, dtype, pipeline, args.cpu_seconds)
 
     if rank == 0:
@@ -951,13 +969,15 @@ def run(args, world, rank, local):
                                    "HIP events around every launch (engine timer)" if args.launch == "direct"
                                    else "none") if events_timed else
                                   "none inside the timed region (overlapping launches): the kernels are timed by the "
-                                  "one-context pass of roofline.duration_from" if events else "none"),
+                                  "one-context pass of roofline.duration_from" if events and args.full else "none"),
                 "kernels": kernels if events_timed else kkernels if roof else {},
                 "other_accumulation": alt,
             },
             "weak_scaling": weak,
             "roofline": roof,
             "cpu_baseline": cpu,
+            "full": args.full,
+            "outputs": dumped,
         }
         print(json.dumps(line), flush=True)
     if world > 1:
@@ -982,6 +1002,65 @@ def committed_traffic(config, fam, rows=0):
         return b, (src if b is not None else None)
     except Exception:
         return None, None
+
+
+DUMP_SEED, DUMP_ROWS, DUMP_BYTES = 42, 64, 32 << 20
+
+
+def dump_sample(Bg, N, row_bytes):
+    """The rows and columns of --dump-outputs: a function of the shape alone.  DUMP_ROWS rows of the GLOBAL
+    batch (the first, the last and a seeded draw, ascending), every column -- or, where those rows exceed
+    DUMP_BYTES (row_bytes = bytes of all output planes per column of one row; db8-stream's 2^20-sample
+    rows), a seeded ascending draw of columns that fits."""
+    import numpy as np
+
+    rng = np.random.default_rng(DUMP_SEED)
+    n_r = min(Bg, DUMP_ROWS)
+    rows = np.unique(np.concatenate(([0, Bg - 1], rng.choice(Bg, n_r, replace=False))))[:n_r]
+    rows[-1] = Bg - 1
+    n_c = min(N, DUMP_BYTES // (len(rows) * row_bytes))
+    cols = None if n_c == N else np.sort(rng.choice(N, n_c, replace=False))
+    return rows, cols
+
+
+def dump_outputs(torch, wl, out_dir, Bg, start, world, rank):
+    """--dump-outputs: what the last timed step left in its buffer set -- the arrays a caller of the timed
+    path receives (fwd+inv: det (J, rows, N), app, y; denoise: y, thr) -- as DIR/<name>.npy in the
+    computation's own dtype, on the sample of dump_sample().  With N > 1 ranks each rank writes the sampled
+    rows it owns as DIR/<name>.rank<r>.npy."""
+    import numpy as np
+
+    names = ("det", "app", "y") if wl.pipeline == "fwd+inv" else ("y", "thr")
+    esz = 4 if wl.f32 else 8
+    rows, cols = dump_sample(Bg, wl.N, (wl.J + 2) * esz if wl.pipeline == "fwd+inv" else esz)
+    torch.cuda.synchronize()
+    got = {k: [] for k in names}
+    off = start
+    for pt in wl.parts:
+        loc = rows[(rows >= off) & (rows < off + pt.rows)] - off
+        off += pt.rows
+        if not len(loc):
+            continue
+        ri = torch.as_tensor(loc, device=pt.x.device)
+        ci = None if cols is None else torch.as_tensor(cols, device=pt.x.device)
+        for k in names:
+            t = getattr(pt, k)                       # the set the last timed step used (Part.last)
+            t = t.index_select(t.dim() - 2 if t.dim() > 1 else 0, ri)
+            if ci is not None and t.dim() > 1:
+                t = t.index_select(t.dim() - 1, ci)
+            got[k].append(t.cpu().numpy())
+    os.makedirs(out_dir, exist_ok=True)
+    shapes = {}
+    for k in names:
+        if not got[k]:
+            continue
+        a = np.concatenate(got[k], axis=got[k][0].ndim - 2 if got[k][0].ndim > 1 else 0)
+        np.save(os.path.join(out_dir, f"{k}.npy" if world == 1 else f"{k}.rank{rank}.npy"), a)
+        shapes[k] = list(a.shape)
+    mine = rows[(rows >= start) & (rows < off)]
+    return {"arrays": shapes, "rows": [int(r) for r in mine], "columns": "all" if cols is None else len(cols),
+            "sample": f"numpy default_rng({DUMP_SEED}): {len(rows)} rows of the global batch"
+                      + ("" if cols is None else f", {len(cols)} columns")}
 
 
 def verify(torch, wl, w, J, pipeline, flags, nat):

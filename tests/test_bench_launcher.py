@@ -169,3 +169,34 @@ def test_schedule_policy_per_shape():
     a.contexts = 3
     K, ov, _ = bench.plan_schedule(a, 512, 4096, 8, cus, "fwd+inv")
     assert not ov and K == 3
+
+
+def test_plain_run_is_the_default_and_full_is_an_option():
+    import bench
+    a = bench.parse(["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert not a.full and a.dump_outputs == "" and a.steps == 7 and a.warmup == 2
+    a = bench.parse(["--full", "--dump-outputs", "d"])
+    assert a.full and a.dump_outputs == "d"
+
+
+@pytest.mark.parametrize("config", sorted(__import__("bench").CONFIGS))
+def test_dump_sample_is_fixed_and_fits(config):
+    # --dump-outputs: the sampled rows / columns depend on the shape alone (two builds dump the same
+    # elements), hold the batch's first and last row, and all output planes together stay under 64 MB
+    import bench
+    _, J, Bg, N, dtype, pipeline = bench.CONFIGS[config]
+    esz = 4 if dtype == "f32" else 8
+    row_bytes = (J + 2) * esz if pipeline == "fwd+inv" else esz
+    rows, cols = bench.dump_sample(Bg, N, row_bytes)
+    rows2, cols2 = bench.dump_sample(Bg, N, row_bytes)
+    assert list(rows) == list(rows2) and (cols is None) == (cols2 is None)
+    assert cols is None or list(cols) == list(cols2)
+    assert rows[0] == 0 and rows[-1] == Bg - 1 and len(rows) == min(Bg, bench.DUMP_ROWS)
+    assert all(b > a for a, b in zip(rows, rows[1:]))
+    assert cols is None or (all(b > a for a, b in zip(cols, cols[1:])) and 0 <= cols[0] and cols[-1] < N)
+    n_c = N if cols is None else len(cols)
+    assert n_c >= min(N, 4096)
+    assert len(rows) * n_c * row_bytes + (8 * len(rows) if pipeline == "denoise" else 0) <= 64 * 10**6
+    assert (cols is None) == (config != "db8-stream")   # only the 2^20-sample rows need a column sample
+    r1, _ = bench.dump_sample(1, 8, 8)
+    assert list(r1) == [0]

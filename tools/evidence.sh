@@ -6,9 +6,10 @@
 # the run.  EVIDENCE_STEPS overrides the step list, e.g. EVIDENCE_STEPS="smoke: cfg:db4".
 set -u
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}" || exit 2
-mkdir -p gpurun_out
-timeout -k 10 300 python bench.py > gpurun_out/bench_driver.json 2> gpurun_out/bench_driver.err || exit $?
-tail -c 400 gpurun_out/bench_driver.json; echo
+export OUT_DIR="${OUT_DIR:-bench_out}"   # where logs and results go
+mkdir -p "$OUT_DIR"
+timeout -k 10 300 python bench.py --full > $OUT_DIR/bench_driver.json 2> $OUT_DIR/bench_driver.err || exit $?
+tail -c 400 $OUT_DIR/bench_driver.json; echo
 # shellcheck disable=SC2086
 bash tools/gpu_steps.sh ${EVIDENCE_STEPS:-t:all smoke: "grp:--steps 20 --warmup 5 --no-alt" \
   "pmc:db4:--contexts 1 --settle 0" cfg:sym8-denoise cfg:db8-stream cfg:coif5-f32 rehearse:2 rehearse:8}

@@ -2,10 +2,10 @@
 # PMC passes over a short bench run (one counter group per rocprofv3 invocation; no tracing domains).
 set -u
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
-PMC_DIR="${PMC_DIR:-gpurun_out/pmc}"
+PMC_DIR="${PMC_DIR:-${OUT_DIR:-bench_out}/pmc}"
 mkdir -p "$PMC_DIR"
 export TMPDIR=/tmp
-ARGS="${BENCH_ARGS:-} --no-cpu-baseline --no-alt --steps 3 --warmup 1"
+ARGS="${BENCH_ARGS:-} --full --no-cpu-baseline --no-alt --steps 3 --warmup 1"
 i=0
 while read -r grp; do
   [ -z "$grp" ] && continue
