@@ -30,6 +30,11 @@
  *                             core/denoising/WaveletDenoiser.java:111-549
  *   vw_transpose_*          BatchSIMDMODWT.convertToSoA / convertFromSoA  ext/extensions/modwt/BatchSIMDMODWT.java:282-308
  *   vw_stream_*             BatchStreamingMODWT  ext/extensions/modwt/BatchStreamingMODWT.java:55-275
+ *   vw_fin_analyze_*        FinancialAnalyzer.analyzeCrashAsymmetry / analyzeVolatility / analyzeRegimeTrend /
+ *                             detectAnomalies  fin/FinancialAnalyzer.java:52-198
+ *                             (fin/ = vectorwave-core/src/main/java/com/morphiqlabs/financial/)
+ *   vw_fin_sharpe_*         FinancialWaveletAnalyzer.calculateSharpeRatio  fin/FinancialWaveletAnalyzer.java:95-124
+ *   vw_fin_wavelet_sharpe_* FinancialWaveletAnalyzer.calculateWaveletSharpeRatio  fin/FinancialWaveletAnalyzer.java:166-212
  *   vw_max_levels           MultiLevelMODWTTransform.getMaximumLevels  core/modwt/MultiLevelMODWTTransform.java:455-501, :693-695
  *   status codes            core/exception/ErrorCode.java:24-118 (see the table below)
  *
@@ -137,7 +142,12 @@ enum {
      * (vw_stream_*) ZERO / SYMMETRIC blocks and flushes are covered too: the history convolution
      * (BatchSIMDMODWT.generalBatchMODWTSoAWithScaledFiltersAndHistory :447-507) multiplies every tap, and
      * the recomputed rows rewrite the histories they leave for the next block. */
-    VW_FLAG_REF_NONFINITE = 1u << 8
+    VW_FLAG_REF_NONFINITE = 1u << 8,
+    /* Financial calls (vw_fin_*): every sum may be a wave / workgroup tree reduction instead of the
+     * reference's sequential loop.  Default (flag clear): one lane adds in index order, bit-identical to
+     * com.morphiqlabs.financial; the dependent fp64 adds of that walk then bound the call.  The
+     * convolution stays EXACT either way. */
+    VW_FLAG_TREE_SUMS = 1u << 9
 };
 
 /* ---- context ---------------------------------------------------------- */
@@ -238,6 +248,45 @@ VW_API vw_status vw_modwt1_forward_f64(vw_ctx *ctx, const double *x, int64_t B, 
 VW_API vw_status vw_modwt1_inverse_f64(vw_ctx *ctx, const double *approx, const double *detail,
                                        int64_t B, int64_t N, const double *lo, const double *hi, int L,
                                        int boundary, unsigned flags, double *y);
+
+/* ---- financial analytics (com.morphiqlabs.financial) ---------------------------------------------
+ * One fused launch per call: each row is read from HBM once, its returns and level-1 PERIODIC MODWT
+ * coefficients live in LDS, and only the reduced doubles are written.  Row length (N - 1 returns for
+ * analyze, N for the Sharpe calls) is at most 16384 (VW_ERR_UNSUPPORTED beyond, as SURE); L <= 30.
+ * Flags: VW_FLAG_HOST_MEMORY, VW_FLAG_SYNC, VW_FLAG_VALIDATE, VW_FLAG_TREE_SUMS.  VW_FLAG_FMA is refused
+ * (VW_ERR_ARG): real prices are quantised, so many level-1 details are exactly 0.0 in EXACT arithmetic and
+ * the reference's `detail > 0 / < 0` classification counts them as neither; a fused multiply-add leaves a
+ * rounding residue there, turning zeros into signed values and changing the counts, not just the last bit.
+ * Without HOST_MEMORY / VALIDATE / SYNC the calls can be recorded into a vw_graph (nothing is allocated
+ * after the first call of a shape). */
+
+/* FinancialAnalyzer (fin/FinancialAnalyzer.java), transform fixed by the caller's taps (the reference uses
+ * DB4), PERIODIC.  Per price row p[0..N): returns r[i] = (p[i+1]-p[i])/p[i] when |p[i]| > 1e-10 else 0.0
+ * (calculateReturns :248-265), d / a = level-1 MODWT of r (vw_modwt1_forward_f64's EXACT arithmetic, any
+ * n = N-1 >= 1), then out[0][b] analyzeCrashAsymmetry :52-91, out[1][b] analyzeVolatility :103-120,
+ * out[2][b] analyzeRegimeTrend :132-154, out[3][b] detectAnomalies :166-198 with threshold anomaly_k (1.0 /
+ * 0.0), out[4][b] the detail standard deviation detectAnomalies compares against.  out is [5][B].
+ * Errors: N < 2 VW_ERR_ARG (validatePrices :270-276).  With VW_FLAG_VALIDATE: a non-finite price is
+ * VW_ERR_ARG "Prices must contain only finite values" (:279-283), else a return that overflows to +-Inf
+ * is VW_ERR_NONFINITE (transform.forward's validation); vw_last_error_index() = b*N + i of the first such
+ * price p[i] (any non-finite price comes before any overflowed return), else of the first such return
+ * r[i], b counted from vw_set_signal_base.  Without it such rows give unspecified values. */
+VW_API vw_status vw_fin_analyze_f64(vw_ctx *ctx, const double *prices, int64_t B, int64_t N, int64_t ld,
+                                    const double *lo, const double *hi, int L, double anomaly_k,
+                                    unsigned flags, double *out);
+/* FinancialWaveletAnalyzer.calculateSharpeRatio(returns, riskFreeRate) :95-124, :234-255 per row:
+ * sequential mean, sequential sum of squared deviations, sample standard deviation (n - 1); a zero
+ * deviation gives 0.0 when mean == risk_free, else +-Inf.  N == 0 VW_ERR_EMPTY, N == 1 VW_ERR_ARG. */
+VW_API vw_status vw_fin_sharpe_f64(vw_ctx *ctx, const double *returns, int64_t B, int64_t N, int64_t ld,
+                                   double risk_free, unsigned flags, double *out);
+/* FinancialWaveletAnalyzer.calculateWaveletSharpeRatio(returns, riskFreeRate) :166-212: level-1 forward,
+ * inverse with an all-zero detail array (bit-identical to vw_modwt1_inverse_f64 on a zero plane), then the
+ * ratio above.  PERIODIC is one launch; ZERO_PADDING / SYMMETRIC run the single-level kernels in the
+ * context workspace first.  N == 1 VW_ERR_ARG (the same check, reached after the transform);
+ * VW_FLAG_VALIDATE: non-finite input VW_ERR_NONFINITE, as vw_modwt1_forward_f64. */
+VW_API vw_status vw_fin_wavelet_sharpe_f64(vw_ctx *ctx, const double *returns, int64_t B, int64_t N, int64_t ld,
+                                           const double *lo, const double *hi, int L, int boundary,
+                                           double risk_free, unsigned flags, double *out);
 
 /* ---- SWT denoise -------------------------------------------------------- */
 /* threshold < 0: universal threshold sigma*sqrt(2 ln N), sigma = median(|d_1|)/0.6745 per signal;

@@ -55,6 +55,8 @@ public final class AmdNative {
     public static final int FLAG_BATCH_HAAR = 1 << 7;
     /** Unvalidated callers: NaN / +-Inf spread through the zero taps exactly as the reference's loops. */
     public static final int FLAG_REF_NONFINITE = 1 << 8;
+    /** Financial calls: tree reductions instead of the reference's sequential sums (not bit-identical). */
+    public static final int FLAG_TREE_SUMS = 1 << 9;
 
     // include/vectorwave_amd.h status codes
     static final int VW_OK = 0, VW_ERR_NULL = 1, VW_ERR_EMPTY = 2, VW_ERR_NONFINITE = 3, VW_ERR_LEVEL = 4,
@@ -101,6 +103,14 @@ public final class AmdNative {
                                       int waveletId, int boundary, int flags, double[][] y);
     static native int swtDenoiseAoS(long ctx, double[][] x, double[] lo, double[] hi, int waveletId, int boundary,
                                     int J, double threshold, boolean soft, int flags, double[][] y);
+
+    // com.morphiqlabs.financial: FinancialAnalyzer's four metrics + the detail standard deviation of every price
+    // row (out: 5 * B doubles, [5][B]); FinancialWaveletAnalyzer's Sharpe ratios of every return row (out: B)
+    static native int finAnalyzeAoS(long ctx, double[][] prices, double[] lo, double[] hi, double anomalyK, int flags,
+                                    double[] out);
+    static native int finSharpeAoS(long ctx, double[][] returns, double riskFree, int flags, double[] out);
+    static native int finWaveletSharpeAoS(long ctx, double[][] returns, double[] lo, double[] hi, int boundary,
+                                          double riskFree, int flags, double[] out);
 
     // VectorWaveSwtAdapter.estimateNoiseSigma per row of B x N coefficients (exact median on the device)
     static native int noiseSigma(long ctx, double[] coeffs, int B, int N, double[] sigmaOut);

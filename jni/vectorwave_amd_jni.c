@@ -558,6 +558,109 @@ JNIEXPORT jint JNICALL VW_JNI(swtDenoiseAoS)(JNIEnv *e, jclass c, jlong ctx, job
   return st;
 }
 
+/* ---- com.morphiqlabs.financial (FinancialAnalyzer.java:52-198, FinancialWaveletAnalyzer.java:95-212) over
+ * vw_fin_*: a double[][] of price / return rows in, a flat double[] of per-row results out ([5][B] for the
+ * analysis: asymmetry, volatility, regime trend, anomaly flag, detail standard deviation).  Rows are chunked
+ * like the other AoS natives; a null batch or row is a NullPointerException, a ragged row an
+ * IllegalArgumentException.  Rows may be short (1 price, 0 returns): the engine reports those. */
+static jsize fin_row_len(JNIEnv *e, jobjectArray rows, const char *what) {
+  if (!rows) { null_error(e, what); return -1; }
+  if ((*e)->GetArrayLength(e, rows) < 1) { arg_error(e, "the batch must hold at least one series"); return -1; }
+  jdoubleArray r = (jdoubleArray)(*e)->GetObjectArrayElement(e, rows, 0);
+  if (!r) { null_error(e, what); return -1; }
+  jsize n = (*e)->GetArrayLength(e, r);
+  (*e)->DeleteLocalRef(e, r);
+  return n;
+}
+
+static int fin_gather_rows(JNIEnv *e, jobjectArray rows, jsize b0, jsize nb, jsize n, double *dst, const char *what) {
+  for (jsize b = 0; b < nb; ++b) {
+    jdoubleArray r = (jdoubleArray)(*e)->GetObjectArrayElement(e, rows, b0 + b);
+    if (!r) { null_error(e, what); return 0; }
+    int ok = (*e)->GetArrayLength(e, r) == n;
+    if (ok && n) (*e)->GetDoubleArrayRegion(e, r, 0, n, dst + (size_t)b * (size_t)n);
+    (*e)->DeleteLocalRef(e, r);
+    if (!ok) { arg_error(e, "all series must have the same length"); return 0; }
+  }
+  return 1;
+}
+
+static int fin_out_ok(JNIEnv *e, jdoubleArray out, size_t need) {
+  if (!out) { null_error(e, "output array cannot be null"); return 0; }
+  if (alen(e, out) < need) { arg_error(e, "output array shorter than the results of the batch"); return 0; }
+  return 1;
+}
+
+JNIEXPORT jint JNICALL VW_JNI(finAnalyzeAoS)(JNIEnv *e, jclass c, jlong ctx, jobjectArray prices, jdoubleArray lo,
+                                             jdoubleArray hi, jdouble anomalyK, jint flags, jdoubleArray out) {
+  (void)c;
+  Taps tl, th;
+  if (!get_taps(e, lo, hi, &tl, &th)) return VW_ERR_ARG;
+  const jsize N = fin_row_len(e, prices, "Prices cannot be null");
+  if (N < 0) return VW_ERR_ARG;
+  const jsize B = (*e)->GetArrayLength(e, prices);
+  if (!fin_out_ok(e, out, (size_t)5 * (size_t)B)) return VW_ERR_ARG;
+  const jsize CB = chunk_rows((size_t)N + 5, B);
+  int oom = 0;
+  double *px = out_buf(0, (size_t)CB * N, &oom), *po = out_buf(1, (size_t)5 * CB, &oom);
+  if (oom) return oom_error(e);
+  vw_status st = VW_OK;
+  for (jsize b0 = 0; b0 < B && st == VW_OK; b0 += CB) {
+    const jsize nb = B - b0 < CB ? B - b0 : CB;
+    if (!fin_gather_rows(e, prices, b0, nb, N, px, "Prices cannot be null")) { st = VW_ERR_ARG; break; }
+    vw_set_signal_base(b0);
+    st = vw_fin_analyze_f64(CTX(ctx), px, nb, N, N, tl.v, th.v, tl.n, anomalyK, (unsigned)flags | HOST_FLAGS, po);
+    vw_set_signal_base(0);
+    for (jsize k = 0; k < 5 && st == VW_OK; ++k)  /* chunk plane k -> out[k][b0 .. b0+nb) */
+      (*e)->SetDoubleArrayRegion(e, out, k * B + b0, nb, po + (size_t)k * nb);
+  }
+  trim_slots();
+  return st;
+}
+
+/* lo == NULL: vw_fin_sharpe_f64; else vw_fin_wavelet_sharpe_f64 */
+static jint fin_sharpe_rows(JNIEnv *e, jlong ctx, jobjectArray returns, const Taps *tl, const Taps *th, jint boundary,
+                            jdouble riskFree, jint flags, jdoubleArray out) {
+  const jsize N = fin_row_len(e, returns, "Returns array cannot be null");
+  if (N < 0) return VW_ERR_ARG;
+  const jsize B = (*e)->GetArrayLength(e, returns);
+  if (!fin_out_ok(e, out, (size_t)B)) return VW_ERR_ARG;
+  const jsize CB = chunk_rows((size_t)N + 1, B);
+  int oom = 0;
+  double *px = out_buf(0, (size_t)CB * N, &oom), *po = out_buf(1, (size_t)CB, &oom);
+  if (oom) return oom_error(e);
+  vw_status st = VW_OK;
+  for (jsize b0 = 0; b0 < B && st == VW_OK; b0 += CB) {
+    const jsize nb = B - b0 < CB ? B - b0 : CB;
+    if (!fin_gather_rows(e, returns, b0, nb, N, px, "Returns array cannot be null")) { st = VW_ERR_ARG; break; }
+    vw_set_signal_base(b0);
+    if (tl)
+      st = vw_fin_wavelet_sharpe_f64(CTX(ctx), px, nb, N, N, tl->v, th->v, tl->n, boundary, riskFree,
+                                     (unsigned)flags | HOST_FLAGS, po);
+    else
+      st = vw_fin_sharpe_f64(CTX(ctx), px, nb, N, N, riskFree, (unsigned)flags | HOST_FLAGS, po);
+    vw_set_signal_base(0);
+    if (st == VW_OK) (*e)->SetDoubleArrayRegion(e, out, b0, nb, po);
+  }
+  trim_slots();
+  return st;
+}
+
+JNIEXPORT jint JNICALL VW_JNI(finSharpeAoS)(JNIEnv *e, jclass c, jlong ctx, jobjectArray returns, jdouble riskFree,
+                                            jint flags, jdoubleArray out) {
+  (void)c;
+  return fin_sharpe_rows(e, ctx, returns, NULL, NULL, 0, riskFree, flags, out);
+}
+
+JNIEXPORT jint JNICALL VW_JNI(finWaveletSharpeAoS)(JNIEnv *e, jclass c, jlong ctx, jobjectArray returns,
+                                                   jdoubleArray lo, jdoubleArray hi, jint boundary, jdouble riskFree,
+                                                   jint flags, jdoubleArray out) {
+  (void)c;
+  Taps tl, th;
+  if (!get_taps(e, lo, hi, &tl, &th)) return VW_ERR_ARG;
+  return fin_sharpe_rows(e, ctx, returns, &tl, &th, boundary, riskFree, flags, out);
+}
+
 /* ---- BatchStreamingMODWT ZERO_PADDING / SYMMETRIC (ext/extensions/modwt/BatchStreamingMODWT.java:55-380)
  * over vw_stream_*: the per-level left history lives on the device between blocks.  (PERIODIC blocks are
  * independent: the Java facade sends them through the BatchMODWT natives, as the reference does.)  A block

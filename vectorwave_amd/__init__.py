@@ -7,6 +7,7 @@ include/vectorwave_amd.h).  This package is the host-side mirror of the referenc
   MutableMultiLevelMODWTResult, BoundaryMode                  (core/modwt, core/api)
   VectorWaveSwtAdapter                                        (core/swt)
   WaveletDenoiser                                             (core/denoising)
+  FinancialAnalyzer, FinancialWaveletAnalyzer and their configs (com.morphiqlabs.financial)
   MODWTStreamingTransform, MultiLevelMODWTStreamingTransform  (core/modwt/streaming)
   BatchMODWT, BatchStreamingMODWT                             (ext/extensions/modwt)
   Haar, Daubechies, Symlet, Coiflet                           (core/api wavelets)
@@ -21,6 +22,8 @@ from .denoise import ThresholdMethod, ThresholdType, WaveletDenoiser
 from .streaming import (MODWTStreamingDenoiser, MODWTStreamingTransform, MODWTStreamingTransformImpl,
                         MultiLevelMODWTStreamingTransform)
 from .batch import BatchMODWT, BatchSIMDMODWT, BatchStreamingMODWT
+from .financial import (FinancialAnalysisConfig, FinancialAnalyzer, FinancialConfig, FinancialWaveletAnalyzer,
+                        VolatilityClassification)
 from .engine import Engine, max_levels, version
 from .multidevice import DeviceGroup
 
@@ -32,4 +35,6 @@ __all__ = [
     "WaveletDenoiser", "ThresholdMethod", "ThresholdType", "BatchSIMDMODWT", "MODWTStreamingTransform",
     "MODWTStreamingTransformImpl", "MultiLevelMODWTStreamingTransform",
     "BatchStreamingMODWT", "Engine", "max_levels", "version", "DeviceGroup",
+    "FinancialAnalysisConfig", "FinancialAnalyzer", "FinancialConfig", "FinancialWaveletAnalyzer",
+    "VolatilityClassification",
 ]

@@ -23,6 +23,7 @@ FLAG_SYNC = 1 << 5
 FLAG_BATCH_SYM_INVERSE = 1 << 6
 FLAG_BATCH_HAAR = 1 << 7
 FLAG_REF_NONFINITE = 1 << 8
+FLAG_TREE_SUMS = 1 << 9
 
 PERIODIC, SYMMETRIC, ZERO_PADDING = 0, 1, 2
 
@@ -66,6 +67,11 @@ SIGNATURES = {
                                       c_void_p, c_void_p]),
     "vw_modwt1_inverse_f64": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int64, _dp, _dp, c_int, c_int, c_uint,
                                       c_void_p]),
+    "vw_fin_analyze_f64": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int64, _dp, _dp, c_int, c_double, c_uint,
+                                   c_void_p]),
+    "vw_fin_sharpe_f64": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int64, c_double, c_uint, c_void_p]),
+    "vw_fin_wavelet_sharpe_f64": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int64, _dp, _dp, c_int, c_int,
+                                          c_double, c_uint, c_void_p]),
     "vw_swt_denoise_f64": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int64, _dp, _dp, c_int, c_int, c_int,
                                    c_int, c_double, c_int, c_uint, c_void_p, c_void_p]),
     "vw_wavelet_denoise_f64": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int64, _dp, _dp, c_int, c_int, c_int,

@@ -2287,6 +2287,207 @@ extern "C" vw_status vw_modwt1_inverse_f64(vw_ctx* c, const double* approx, cons
 }
 
 // ------------------------------------------------------------------------------------------------
+// com.morphiqlabs.financial (vw_fin.hip): FinancialAnalyzer's four metrics and FinancialWaveletAnalyzer's
+// Sharpe ratios, one workgroup per row, one launch per call (the non-periodic wavelet Sharpe composes the
+// single-level forward and inverse in ws2 first).
+
+static vw_status fin_common(vw_ctx* c, const void* in, const void* out, int64_t B, unsigned flags) {
+  if (!c) return fail(VW_ERR_NULL, "ctx is null");
+  if (!in || !out) return fail(VW_ERR_NULL, "null array argument");
+  if (B <= 0) return fail(VW_ERR_EMPTY, "batch must be non-empty (B=%lld)", (long long)B);
+  if (flags & VW_FLAG_FMA)
+    return fail(VW_ERR_ARG, "VW_FLAG_FMA is not supported by the financial calls (fused taps change the detail signs)");
+  return VW_OK;
+}
+
+static vw_status fin_taps(const double* lo, const double* hi, int L, FinArgs* a) {
+  if (!lo || !hi) return fail(VW_ERR_NULL, "null filter argument");
+  if (L < 1 || L > kFinMaxTaps) return fail(VW_ERR_ARG, "filter length %d unsupported (1..%d)", L, kFinMaxTaps);
+  const double s = 1.0 / std::sqrt(2.0);  // as copy_taps
+  for (int i = 0; i < kFinMaxTaps; ++i) {
+    a->lo[i] = i < L ? lo[i] * s : 0.0;
+    a->hi[i] = i < L ? hi[i] * s : 0.0;
+  }
+  a->L = L;
+  return VW_OK;
+}
+
+// the kernel's validation word -> status.  Bit 62: a return that overflowed between two finite prices
+// (the reference's transform.forward rejects it); clear: a non-finite input element.
+static vw_status fin_report(unsigned long long bad, int64_t N, bool prices) {
+  if (bad == ~0ull) return VW_OK;
+  const bool overflow = (bad >> 62) & 1ull;
+  const unsigned long long flat = bad & ((1ull << 62) - 1);
+  const long long i = (long long)(flat % (unsigned long long)N);
+  const long long b = (long long)(flat / (unsigned long long)N) + (long long)t_signal_base;
+  vw_status st;
+  if (prices && !overflow)
+    st = fail(VW_ERR_ARG, "Prices must contain only finite values (index %lld, signal %lld)", i, b);
+  else
+    st = fail(VW_ERR_NONFINITE, "%s contains non-finite value at index %lld (signal %lld)",
+              prices ? "returns" : "signal", i, b);
+  t_err_index = (int64_t)(b * (long long)N + i);
+  return st;
+}
+
+static vw_status fin_launch(vw_ctx* c, const FinArgs& a, bool analyze, unsigned flags) {
+  if (a.validate) VW_HIP(hipMemsetAsync(c->bad, 0xFF, sizeof(unsigned long long), c->stream));
+  {
+    LaunchTimer lt(c, "fin");
+    hipError_t e = analyze ? launch_fin_analyze(a, c->stream) : launch_fin_sharpe(a, c->stream);
+    if (e != hipSuccess) return fail(VW_ERR_DEVICE, "launch failed: %s", hipGetErrorString(e));
+  }
+  if (a.validate) {
+    unsigned long long bad = ~0ull;
+    VW_TRY(read_bad(c, &bad));
+    VW_TRY(fin_report(bad, a.N, analyze));
+  }
+  if (flags & VW_FLAG_SYNC) VW_HIP(hipStreamSynchronize(c->stream));
+  return VW_OK;
+}
+
+extern "C" vw_status vw_fin_analyze_f64(vw_ctx* c, const double* prices, int64_t B, int64_t N, int64_t ld,
+                                        const double* lo, const double* hi, int L, double anomaly_k, unsigned flags,
+                                        double* out) {
+  VW_TRY(fin_common(c, prices, out, B, flags));
+  FinArgs a{};
+  VW_TRY(fin_taps(lo, hi, L, &a));
+  if (N < 2) return fail(VW_ERR_ARG, "Prices must contain at least 2 elements");
+  if (ld < N) return fail(VW_ERR_ARG, "ld (%lld) < N (%lld)", (long long)ld, (long long)N);
+  if (N - 1 > kFinMaxN)
+    return fail(VW_ERR_UNSUPPORTED, "financial analysis keeps a row's coefficients in LDS: at most %d returns per row",
+                kFinMaxN);
+  std::lock_guard<std::recursive_mutex> g(c->mu);
+  hipSetDevice(c->device);
+  VW_TRY(capture_guard(c, flags));
+  a.B = B; a.N = (int)N; a.ld = ld; a.k = anomaly_k;
+  a.tree = (flags & VW_FLAG_TREE_SUMS) ? 1 : 0;
+  a.validate = (flags & VW_FLAG_VALIDATE) ? 1 : 0;
+  a.bad = c->bad;
+  if (flags & VW_FLAG_HOST_MEMORY) {
+    Staging s(c);
+    double *dp, *dout;
+    VW_TRY(s.in(prices, (size_t)(B - 1) * ld + N, &dp));
+    VW_TRY(s.in<double>(nullptr, (size_t)5 * B, &dout));
+    a.x = dp; a.out = dout;
+    VW_TRY(fin_launch(c, a, true, 0));
+    VW_TRY(s.out(out, dout, (size_t)5 * B));
+    VW_HIP(hipStreamSynchronize(c->stream));
+    return ok();
+  }
+  a.x = prices; a.out = out;
+  VW_TRY(fin_launch(c, a, true, flags));
+  return ok();
+}
+
+static const char* const kSingleReturnMsg =
+    "Cannot calculate Sharpe ratio with a single return value. "
+    "At least 2 returns are required to calculate standard deviation (risk).";
+
+static vw_status fin_sharpe_checks(int64_t N, int64_t ld) {
+  if (N <= 0) return fail(VW_ERR_EMPTY, "Returns array cannot be empty");
+  if (N == 1) return fail(VW_ERR_ARG, "%s", kSingleReturnMsg);
+  if (ld < N) return fail(VW_ERR_ARG, "ld (%lld) < N (%lld)", (long long)ld, (long long)N);
+  if (N > kFinMaxN)
+    return fail(VW_ERR_UNSUPPORTED, "the Sharpe calls keep a row in LDS: at most %d returns per row", kFinMaxN);
+  return VW_OK;
+}
+
+extern "C" vw_status vw_fin_sharpe_f64(vw_ctx* c, const double* returns, int64_t B, int64_t N, int64_t ld,
+                                       double risk_free, unsigned flags, double* out) {
+  VW_TRY(fin_common(c, returns, out, B, flags));
+  VW_TRY(fin_sharpe_checks(N, ld));
+  std::lock_guard<std::recursive_mutex> g(c->mu);
+  hipSetDevice(c->device);
+  VW_TRY(capture_guard(c, flags));
+  FinArgs a{};
+  a.B = B; a.N = (int)N; a.ld = ld; a.k = risk_free;
+  a.tree = (flags & VW_FLAG_TREE_SUMS) ? 1 : 0;
+  a.bad = c->bad;  // (the reference's plain Sharpe ratio does not validate: VW_FLAG_VALIDATE checks nothing here)
+  if (flags & VW_FLAG_HOST_MEMORY) {
+    Staging s(c);
+    double *dr, *dout;
+    VW_TRY(s.in(returns, (size_t)(B - 1) * ld + N, &dr));
+    VW_TRY(s.in<double>(nullptr, (size_t)B, &dout));
+    a.x = dr; a.out = dout;
+    VW_TRY(fin_launch(c, a, false, 0));
+    VW_TRY(s.out(out, dout, (size_t)B));
+    VW_HIP(hipStreamSynchronize(c->stream));
+    return ok();
+  }
+  a.x = returns; a.out = out;
+  VW_TRY(fin_launch(c, a, false, flags));
+  return ok();
+}
+
+// device pointers in, device pointer out
+static vw_status wavelet_sharpe_device(vw_ctx* c, FinArgs a, const double* lo, const double* hi, int boundary,
+                                       unsigned flags) {
+  if (boundary == VW_PERIODIC) {
+    a.wavelet = 1;
+    a.validate = (flags & VW_FLAG_VALIDATE) ? 1 : 0;
+    return fin_launch(c, a, false, flags);
+  }
+  // ZERO_PADDING / SYMMETRIC: the existing single-level kernels, planes approx | detail | y in ws2
+  const size_t plane = (size_t)a.B * (size_t)a.N;
+  const size_t bytes = 3 * plane * sizeof(double);
+  if (bytes > c->ws2_bytes) {
+    if (c->capturing) return fail(VW_ERR_STATE, "workspace growth during capture: run the call once before capturing it");
+    if (c->ws2) {
+      hipDeviceSynchronize();
+      ++c->ws_gen;
+      hipFree(c->ws2);
+      c->ws2 = nullptr;
+      c->ws2_bytes = 0;
+    }
+    VW_HIP(hipMalloc(&c->ws2, bytes));
+    c->ws2_bytes = bytes;
+  }
+  double* da = reinterpret_cast<double*>(c->ws2);
+  double* dd = da + plane;
+  double* dy = dd + plane;
+  const unsigned tf = flags & (VW_FLAG_VALIDATE | VW_FLAG_REF_NONFINITE);
+  VW_TRY(forward_impl<double>(c, a.x, a.B, a.N, a.ld, lo, hi, a.L, boundary, 1, tf, dd, da, true, -1, nullptr, false));
+  VW_HIP(hipMemsetAsync(dd, 0, plane * sizeof(double), c->stream));  // `new double[detailCoeffs.length]`
+  VW_TRY(inverse_impl<double>(c, dd, da, a.B, a.N, lo, hi, a.L, VW_WID_OTHER, boundary, 1, 1u, 0,
+                              tf & ~VW_FLAG_VALIDATE, dy, true, nullptr, 0));
+  a.x = dy;
+  a.ld = a.N;
+  return fin_launch(c, a, false, flags);
+}
+
+extern "C" vw_status vw_fin_wavelet_sharpe_f64(vw_ctx* c, const double* returns, int64_t B, int64_t N, int64_t ld,
+                                               const double* lo, const double* hi, int L, int boundary,
+                                               double risk_free, unsigned flags, double* out) {
+  VW_TRY(fin_common(c, returns, out, B, flags));
+  FinArgs a{};
+  VW_TRY(fin_taps(lo, hi, L, &a));
+  if (boundary < VW_PERIODIC || boundary > VW_ZERO_PADDING)
+    return fail(VW_ERR_BOUNDARY, "MODWT only supports PERIODIC, ZERO_PADDING, and SYMMETRIC boundary modes");
+  VW_TRY(fin_sharpe_checks(N, ld));
+  std::lock_guard<std::recursive_mutex> g(c->mu);
+  hipSetDevice(c->device);
+  VW_TRY(capture_guard(c, flags));
+  a.B = B; a.N = (int)N; a.ld = ld; a.k = risk_free;
+  a.tree = (flags & VW_FLAG_TREE_SUMS) ? 1 : 0;
+  a.bad = c->bad;
+  if (flags & VW_FLAG_HOST_MEMORY) {
+    Staging s(c);
+    double *dr, *dout;
+    VW_TRY(s.in(returns, (size_t)(B - 1) * ld + N, &dr));
+    VW_TRY(s.in<double>(nullptr, (size_t)B, &dout));
+    a.x = dr; a.out = dout;
+    VW_TRY(wavelet_sharpe_device(c, a, lo, hi, boundary, flags & ~(VW_FLAG_SYNC | VW_FLAG_HOST_MEMORY)));
+    VW_TRY(s.out(out, dout, (size_t)B));
+    VW_HIP(hipStreamSynchronize(c->stream));
+    return ok();
+  }
+  a.x = returns; a.out = out;
+  VW_TRY(wavelet_sharpe_device(c, a, lo, hi, boundary, flags));
+  return ok();
+}
+
+// ------------------------------------------------------------------------------------------------
 // SWT denoise: fused forward -> per-signal exact median of |d_1| -> inverse with fused threshold.
 extern "C" vw_status vw_noise_sigma_f64(vw_ctx* c, const double* coeffs, int64_t B, int64_t N, unsigned flags,
                                         double* sigma) {

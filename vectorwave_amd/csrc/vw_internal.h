@@ -240,6 +240,28 @@ int mfma_region(int n);  // LDS floats of the kernels' padded level region for e
 hipError_t launch_forward_mfma(const FwdArgs<float>& a, int lds, hipStream_t st);
 hipError_t launch_inverse_mfma(const InvArgs<float>& a, int lds, hipStream_t st);
 
+// Financial analytics (vw_fin.hip): one workgroup per row, the row's level-1 coefficients in LDS.
+constexpr int kFinMaxN = 16384;    // longest row (returns for analyze, N for the Sharpe calls): 8 * n bytes of LDS
+constexpr int kFinMaxTaps = 30;
+constexpr int kFinPerThread = 16;  // coefficients a thread holds in registers while they replace the row in LDS
+struct FinArgs {
+  const double* x;         // analyze: prices [B][ld], N per row; sharpe: returns [B][ld]
+  long long ld;
+  long long B;
+  int N;
+  int L;
+  int tree;                // 1: tree reductions (VW_FLAG_TREE_SUMS), 0: the reference's sequential sums
+  int validate;            // 1: non-finite inputs (and overflowed returns, bit 62) -> atomicMin into *bad
+  int wavelet;             // sharpe: 1 = level-1 forward + inverse with zero details first (PERIODIC)
+  double k;                // analyze: anomaly threshold in standard deviations; sharpe: risk-free rate
+  double* out;             // analyze: [5][B]; sharpe: [B]
+  unsigned long long* bad;
+  double lo[kFinMaxTaps];  // base taps * 1/sqrt(2), as the transform kernels
+  double hi[kFinMaxTaps];
+};
+hipError_t launch_fin_analyze(const FinArgs& a, hipStream_t st);
+hipError_t launch_fin_sharpe(const FinArgs& a, hipStream_t st);
+
 // Raise a kernel's dynamic-LDS limit past the 64 KiB default once per kernel instantiation AND
 // device (the attribute belongs to the device's copy of the function; a call per launch costs host
 // time).  `once` is a static of the caller, unique per kernel instantiation; several host threads

@@ -250,6 +250,44 @@ class Engine:
                                                self._flags(flags, dev), self._ptr(y, dev), self._ptr(thr, dev)))
         return (y, thr) if want_thresholds else y
 
+    # -- financial analytics (vw_fin_*) -----------------------------------------------------------
+    def _rows(self, x, N):
+        """(array, is_dev, ptr, B, N, ld) of a [N] / [B,ld] float64 input; ``N`` < ld: only the first N columns of
+        each row are data (a non-contiguous leading dimension)."""
+        xa, dev, xp, _ = self._prep(x, np.float64)
+        B, ld = (1, xa.shape[0]) if xa.ndim == 1 else xa.shape
+        n = ld if N is None else int(N)
+        if n > ld:
+            raise ValueError(f"N={n} exceeds the row width {ld}")
+        return xa, dev, xp, B, n, ld
+
+    def fin_analyze(self, prices, lo, hi, anomaly_k: float, flags: int = 0, N: Optional[int] = None):
+        """vw_fin_analyze_f64: prices [N] or [B,N] -> [5,B] (asymmetry, volatility, regimeTrend, anomaly flag,
+        detail std).  ``N``: row length when the array is wider (its width is the leading dimension)."""
+        xa, dev, xp, B, n, ld = self._rows(prices, N)
+        out = self._empty(xa, dev, (5, B))
+        _check(self.lib.vw_fin_analyze_f64(self.ctx, xp, B, n, ld, nat.taps_array(lo), nat.taps_array(hi), len(lo),
+                                           float(anomaly_k), self._flags(flags, dev), self._ptr(out, dev)))
+        return out
+
+    def fin_sharpe(self, returns, risk_free: float, flags: int = 0, N: Optional[int] = None):
+        """vw_fin_sharpe_f64: returns [N] or [B,N] -> [B]."""
+        xa, dev, xp, B, n, ld = self._rows(returns, N)
+        out = self._empty(xa, dev, (B,))
+        _check(self.lib.vw_fin_sharpe_f64(self.ctx, xp, B, n, ld, float(risk_free), self._flags(flags, dev),
+                                          self._ptr(out, dev)))
+        return out
+
+    def fin_wavelet_sharpe(self, returns, lo, hi, boundary: int, risk_free: float, flags: int = 0,
+                           N: Optional[int] = None):
+        """vw_fin_wavelet_sharpe_f64: returns [N] or [B,N] -> [B]."""
+        xa, dev, xp, B, n, ld = self._rows(returns, N)
+        out = self._empty(xa, dev, (B,))
+        _check(self.lib.vw_fin_wavelet_sharpe_f64(self.ctx, xp, B, n, ld, nat.taps_array(lo), nat.taps_array(hi),
+                                                  len(lo), int(boundary), float(risk_free),
+                                                  self._flags(flags, dev), self._ptr(out, dev)))
+        return out
+
     def transpose(self, a, rows: int, cols: int):
         """out[c][r] = a[r][c] (a: rows*cols elements, any shape) -> flat [cols*rows] array."""
         aa, dev, ap, f32 = self._prep(a)
