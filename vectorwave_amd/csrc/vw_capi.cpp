@@ -107,6 +107,8 @@ struct Tuning {
   int sweep2_minb = 64;        // VW_SWEEP2_MINB: blocks a residue class needs for the chained sweeps
   int blk_fwd8 = 1;            // VW_BLK_FWD8=0: fused forward instead of the register-blocked one at NV = 8
   int ref_grid = 0;            // VW_REF_GRID: workgroups of the REF_NONFINITE fix-up launch (0 = 2 per CU)
+  int level_ct = 1;            // VW_LEVEL_CT=0: run-time level strides and bounds-checked slabs in the fused kernels of
+                               // short filters (L <= 8), as before (profiles/r07/ab_db4_level_ct.log)
   int mfma = 0;                // VW_MFMA=1|2|3: fp32 FMA PERIODIC forward (1) / inverse (2) / both (3) on the matrix
                                // cores (vw_mfma.hip)
 };
@@ -152,6 +154,7 @@ static bool set_tuning(Tuning& t, const char* key, int v) {
   else if (k == "VW_SWEEP2_R") t.sweep2_r = v == 32 ? 32 : 0;
   else if (k == "VW_SWEEP2_MINB") t.sweep2_minb = v < 0 ? d.sweep2_minb : v;
   else if (k == "VW_BLK_FWD8") t.blk_fwd8 = v < 0 ? d.blk_fwd8 : v;
+  else if (k == "VW_LEVEL_CT") t.level_ct = v < 0 ? d.level_ct : v != 0;
   else if (k == "VW_MFMA") t.mfma = v < 0 ? d.mfma : v;
   else if (k == "VW_REF_GRID") t.ref_grid = v < 0 ? d.ref_grid : v;
   else return false;
@@ -164,7 +167,7 @@ static const char* const kTuningKeys[] = {
     "VW_UNROLL_MAX", "VW_BLK", "VW_FWD_NV",
     "VW_INV_NV", "VW_DEEP", "VW_DEEP_INV", "VW_DEEP_LDS", "VW_DEEP_WAVES", "VW_DEEP_PF_FWD", "VW_DEEP_PF_INV",
     "VW_SWEEP2", "VW_SWEEP2_KA", "VW_SWEEP2_UC", "VW_SWEEP2_R", "VW_SWEEP2_MINB", "VW_BLK_FWD8",
-    "VW_DMA_NT", "VW_MULTI_NI", "VW_MFMA", "VW_REF_GRID"};
+    "VW_DMA_NT", "VW_MULTI_NI", "VW_MFMA", "VW_REF_GRID", "VW_LEVEL_CT"};
 
 static Tuning read_tuning() {
   Tuning t;
@@ -1306,6 +1309,7 @@ static vw_status forward_impl(vw_ctx* c, const T* x, int64_t B, int64_t N, int64
     a.unrolled = a.vec_io && fit && L <= tu.unroll_max;
     a.validate = validate; a.bad = c->bad;
     a.rev = tu.fwd_rev;
+    a.level_ct = tu.level_ct;
     // non-temporal LDS-DMA of the rows: faster at <= 2 signals per CU (512 rows: forward 0.0268 -> 0.0245 ms),
     // slower on full batches (4096 rows: 0.218-0.225 -> 0.234-0.243 ms; profiles/r04/ab_rotate_default_*.log,
     // ab_overlap_direct_512.log)
@@ -1621,6 +1625,8 @@ static vw_status inverse_impl(vw_ctx* c, const T* details, const T* approx, int6
     a.unrolled = a.vec_io && fit && L <= tu.unroll_max;
     a.pair = pair; a.approx_zero = approx_zero; a.thr = thr; a.thr_ld = thr_ld; a.soft = soft; a.taps = L;
     a.rev = tu.inv_rev;
+    a.level_ct = tu.level_ct;
+    a.full = tu.level_ct && a.unrolled && (int64_t)threads * nv == nvec;
     // register-blocked PERIODIC inverse for long filters (vw_device.h k_inverse_blk)
     if (tu.blk > 0 && L >= tu.blk && nv != 2 && !pair && !db && boundary == VW_PERIODIC && a.unrolled &&
         (int64_t)threads * nv == nvec) {

@@ -372,7 +372,8 @@ __device__ __forceinline__ void inv_pair(const T* A, const T* D, int t0, int S, 
 // fused kernels make every such decision once per level (row functions below, templated on the
 // spacing class and direction), and only the last of a thread's NV vectors carries a bounds check:
 // the host sizes the workgroup so that slabs 0..NV-2 are full ((NV-1)*NT <= nvec, vw_capi.cpp).
-template <int L, int NV, typename F>
+// FULL: every slab is full (threads * NV == nvec, a host contract): no bounds check at all.
+template <int L, int NV, bool FULL = false, typename F>
 __device__ __forceinline__ void for_vecs(int nvec, F&& fn) {
   const int NT = blockDim.x;
 #pragma unroll
@@ -382,7 +383,7 @@ __device__ __forceinline__ void for_vecs(int nvec, F&& fn) {
     // hoisting all of them (every vector x every buffer x every spacing path) out of it exhausts
     // the 128-VGPR budget and spills.  Recomputing them per level costs a few VALU.
     asm volatile("" : "+v"(w));
-    if ((L > 0 && k < NV - 1) || w < nvec) fn(k, w);
+    if (FULL || (L > 0 && k < NV - 1) || w < nvec) fn(k, w);
     // ... and keep the scheduler from issuing the LDS reads of every vector at once (NV x L
     // b128 reads in flight = all the VGPRs); 4 waves per SIMD hide the per-vector read latency.
     __builtin_amdgcn_sched_barrier(0);
@@ -435,11 +436,12 @@ __device__ __forceinline__ V16 stream_load(const T* base, int i) {
   }
 }
 
-template <int AUX = VW_STORE_AUX, typename T>
+// FULL: aligned rows of whole vectors (host contract): no ragged-row test, no scalar fallback.
+template <int AUX = VW_STORE_AUX, bool FULL = false, typename T>
 __device__ __forceinline__ void store_vec(T* __restrict__ dst, int t0, int N, bool vec_ok, const T (&v)[VT<T>::V]) {
   constexpr int V = VT<T>::V;
   using vec = typename VT<T>::v;
-  if (vec_ok && t0 + V <= N) {
+  if (FULL || (vec_ok && t0 + V <= N)) {
     vec o;
 #pragma unroll
     for (int e = 0; e < V; ++e) o[e] = v[e];
@@ -481,7 +483,7 @@ __device__ __forceinline__ T threshold_t(T c, T thr, int soft) {
 // those registers are never used): an exec-masked load in its own basic block makes the waitcnt
 // pass lose count and wait vmcnt(0) at the first use, i.e. for every load in flight.  The unrolled
 // kernels (L > 0) only run on 16-byte-aligned rows; the scalar form is the runtime-L kernel's.
-template <typename T, int NV>
+template <typename T, int NV, bool FULL = false>
 __device__ __forceinline__ void load_row_regs(T (&r)[NV][VT<T>::V], const T* __restrict__ src, int N, int nvec,
                                               bool vec_ok, bool zero) {
   constexpr int V = VT<T>::V;
@@ -493,7 +495,7 @@ __device__ __forceinline__ void load_row_regs(T (&r)[NV][VT<T>::V], const T* __r
     for (int k = 0; k < NV; ++k) {
       int w = (int)threadIdx.x + k * NT;
       asm volatile("" : "+v"(w));  // not hoisted out of the level loop (see for_vecs)
-      w = min(w, nvec - 1);
+      if constexpr (!FULL) w = min(w, nvec - 1);
       const vec v = stream_load<vec>(src, w);
 #pragma unroll
       for (int e = 0; e < V; ++e) r[k][e] = v[e];
@@ -523,13 +525,13 @@ __device__ __forceinline__ void load_row_regs(T (&r)[NV][VT<T>::V], const T* __r
 // Positions with no source (zero padding, fftpad gaps, streaming history) are written by
 // halo_fixed.  When these conditions do not hold the host clears LevelDesc::own and the kernels
 // fill the halo from LDS after a barrier (fill_halo), as the reference's modulo does for any index.
-template <typename T>
+template <typename T, bool FULL = false>
 __device__ __forceinline__ void halo_images(T* buf, int w, const typename VT<T>::v& o, int N, const LevelDesc& lv) {
   constexpr int V = VT<T>::V;
 #pragma unroll
   for (int e = 0; e < V; ++e) {
     const int t = w * V + e;
-    if (t < N) {
+    if (FULL || t < N) {
       const int l = lv.il_a * t + lv.il_b;
       const int r = lv.ir_a * t + lv.ir_b;
       if (l < 0 && l >= -lv.hl) buf[l] = o[e];
@@ -553,13 +555,13 @@ __device__ __forceinline__ void halo_fixed(T* buf, int N, const LevelDesc& lv, i
 
 // Write a register-held row into the LDS level buffer `buf` with its halo for level `lv`.
 // MODE 0: values as is; 1: zeros (masked-out level, registers never loaded); 2: thresholded.
-template <typename T, int L, int NV, int MODE>
+template <typename T, int L, int NV, int MODE, bool FULL = false>
 __device__ __forceinline__ void regs_to_level_m(T* buf, const T (&r)[NV][VT<T>::V], int nvec, int N,
                                                 const LevelDesc& lv, T thr_b, int soft) {
   constexpr int V = VT<T>::V;
   using vec = typename VT<T>::v;
   const bool own = lv.own != 0;
-  for_vecs<L, NV>(nvec, [&](int k, int w) {
+  for_vecs<L, NV, FULL>(nvec, [&](int k, int w) {
     vec o;
 #pragma unroll
     for (int e = 0; e < V; ++e) {
@@ -578,19 +580,19 @@ __device__ __forceinline__ void regs_to_level_m(T* buf, const T (&r)[NV][VT<T>::
       for (int e = 0; e < V; ++e)
         if (w * V + e < N) buf[w * V + e] = o[e];
     }
-    if (own && ((k == 0 && w < lv.vs) || (k == NV - 1 && w >= lv.ve))) halo_images(buf, w, o, N, lv);
+    if (own && ((k == 0 && w < lv.vs) || (k == NV - 1 && w >= lv.ve))) halo_images<T, FULL>(buf, w, o, N, lv);
   });
 }
 
 // If the level cannot use owner writes this ends with a barrier and the generic halo fill; either
 // way the caller's next lds_barrier() publishes data + halo.
-template <typename T, int L, int NV>
+template <typename T, int L, int NV, bool FULL = false>
 __device__ __forceinline__ void regs_to_level(T* buf, const T (&r)[NV][VT<T>::V], int nvec, int N, const LevelDesc& lv,
                                               int npow2, const T* hist_b, bool zero = false, const T* thr = nullptr,
                                               T thr_b = T(0), int soft = 0) {
-  if (zero) regs_to_level_m<T, L, NV, 1>(buf, r, nvec, N, lv, thr_b, soft);
-  else if (thr) regs_to_level_m<T, L, NV, 2>(buf, r, nvec, N, lv, thr_b, soft);
-  else regs_to_level_m<T, L, NV, 0>(buf, r, nvec, N, lv, thr_b, soft);
+  if (zero) regs_to_level_m<T, L, NV, 1, FULL>(buf, r, nvec, N, lv, thr_b, soft);
+  else if (thr) regs_to_level_m<T, L, NV, 2, FULL>(buf, r, nvec, N, lv, thr_b, soft);
+  else regs_to_level_m<T, L, NV, 0, FULL>(buf, r, nvec, N, lv, thr_b, soft);
   if (lv.own) {
     halo_fixed(buf, N, lv, npow2, hist_b);
   } else {
@@ -602,12 +604,12 @@ __device__ __forceinline__ void regs_to_level(T* buf, const T (&r)[NV][VT<T>::V]
 // ---- Row compute: one level's convolution over the thread's NV vectors -------------------------
 // Forward, both filters from one set of LDS reads; emit(k, w, al, ah) consumes each output vector.
 // SC: 1 / 2 = register window for spacing 1 / 2 (the latter fp32 only), 0 = strided b128 reads.
-template <typename T, int L, bool FMA, int NV, int SC, typename Emit>
+template <typename T, int L, bool FMA, int NV, int SC, bool FULL = false, typename Emit>
 __device__ __forceinline__ void fwd_row_t(const T* buf, int nvec, int s, const T* lo, const T* hi, int taps,
                                           Emit&& emit) {
   constexpr int V = VT<T>::V;
   using vec = typename VT<T>::v;
-  for_vecs<L, NV>(nvec, [&](int k, int w) {
+  for_vecs<L, NV, FULL>(nvec, [&](int k, int w) {
     const int t0 = w * V;
     T al[V], ah[V];
 #pragma unroll
@@ -629,29 +631,74 @@ __device__ __forceinline__ void fwd_row_t(const T* buf, int nvec, int s, const T
   });
 }
 
-template <typename T, int L, bool FMA, int NV, typename Emit>
-__device__ __forceinline__ void fwd_row(const T* buf, int nvec, int s, const T* lo, const T* hi, int taps,
+// Strided levels at a COMPILE-TIME spacing S (tap-unrolled short filters): the taps' addresses differ by
+// constants, so one laundered 32-bit LDS base per output vector -- the lowest address of the tap window,
+// every offset non-negative and within the 16-bit field -- serves all L reads as ds_read_b128 base
+// offset:imm.  With a run-time spacing each read pays its own address instruction (a v_lshl_add / v_add /
+// v_subrev per tap: as much issue time as a v_fma_f64).  Same taps, same order, same arithmetic as SC = 0.
+#define VW_CT_SPACINGS(X) X(2) X(4) X(8) X(16) X(32) X(64)
+template <typename T, int L, bool FMA, int NV, int S, bool FULL, typename Emit>
+__device__ __forceinline__ void fwd_row_ct(const T* buf, int nvec, const T* lo, const T* hi, Emit&& emit) {
+  constexpr int V = VT<T>::V;
+  using vec = typename VT<T>::v;
+  static_assert(S % V == 0 && (L - 1) * S * (int)sizeof(T) < 65536, "aligned reads, 16-bit offsets");
+  const T* const low = buf - (L - 1) * S;  // tap L-1, the lowest address (uniform part)
+  for_vecs<L, NV, FULL>(nvec, [&](int k, int w) {
+    const int t0 = w * V;
+    T al[V], ah[V];
+#pragma unroll
+    for (int e = 0; e < V; ++e) { al[e] = T(0); ah[e] = T(0); }
+    const unsigned a0 = lds_base(low + t0);
+#pragma unroll
+    for (int i = 0; i < L; ++i) {
+      const vec v = lds_vec_at<vec>(a0 + (unsigned)((L - 1 - i) * S * (int)sizeof(T)));
+      vmadd<FMA, kPkFwd>(al, v, lo[i]);
+      vmadd<FMA, kPkFwd>(ah, v, hi[i]);
+      // <= 4 reads in flight, as the run-time body; 8 measured the same (profiles/r07/ab_db4_level_ct.log)
+      if ((i & 3) == 3) __builtin_amdgcn_sched_barrier(0);
+    }
+    emit(k, w, al, ah);
+  });
+}
+
+// ct: the level's spacing is dispatched ONCE per row and level to a compile-time-stride body (VW_LEVEL_CT);
+// any other spacing, and ct = 0, run the run-time-stride body.
+template <typename T, int L, bool FMA, int NV, bool FULL = false, typename Emit>
+__device__ __forceinline__ void fwd_row(const T* buf, int nvec, int s, const T* lo, const T* hi, int taps, int ct,
                                         Emit&& emit) {
   constexpr int V = VT<T>::V;
   if constexpr (L > 0) {
-    if (s == 1) return fwd_row_t<T, L, FMA, NV, 1>(buf, nvec, s, lo, hi, taps, emit);
+    if (s == 1) return fwd_row_t<T, L, FMA, NV, 1, FULL>(buf, nvec, s, lo, hi, taps, emit);
     if constexpr (V == 4) {
-      if (s == 2) return fwd_row_t<T, L, FMA, NV, 2>(buf, nvec, s, lo, hi, taps, emit);
+      if (s == 2) return fwd_row_t<T, L, FMA, NV, 2, FULL>(buf, nvec, s, lo, hi, taps, emit);
     }
   }
-  fwd_row_t<T, L, FMA, NV, 0>(buf, nvec, s, lo, hi, taps, emit);
+  if constexpr (L > 0 && L <= 8) {
+    if (ct) {
+      switch (s) {
+#define VW_CASE(n) \
+        case n:    \
+          if constexpr (n % V == 0) return fwd_row_ct<T, L, FMA, NV, n, FULL>(buf, nvec, lo, hi, emit); \
+          break;
+        VW_CT_SPACINGS(VW_CASE)
+#undef VW_CASE
+        default: break;
+      }
+    }
+  }
+  fwd_row_t<T, L, FMA, NV, 0, FULL>(buf, nvec, s, lo, hi, taps, emit);
 }
 
 // Inverse, one branch over the row: acc[k]_e (+)= f[i] * buf[t0 + e + dir*i*s + off], i ascending
 // (MultiLevelMODWTTransform.java:578-588 periodic, :612-639 symmetric orientations).
 // SC as above; SC = -1: generic per-element form (runtime taps, or an offset that is not a
 // multiple of V -- the symmetric alignment shifts).
-template <typename T, int L, bool FMA, int NV, int SC, int DIR>
+template <typename T, int L, bool FMA, int NV, int SC, int DIR, bool FULL = false>
 __device__ __forceinline__ void inv_row_t(const T* buf, int nvec, int s, int dir, int off, const T* f, int taps,
                                           T (&acc)[NV][VT<T>::V]) {
   constexpr int V = VT<T>::V;
   using vec = typename VT<T>::v;
-  for_vecs<L, NV>(nvec, [&](int k, int w) {
+  for_vecs<L, NV, FULL>(nvec, [&](int k, int w) {
     const int t0 = w * V;
     if constexpr (L > 0 && SC > 0) {
       inv_window<T, L, FMA, SC, DIR>(buf, t0 + off, f, acc[k]);
@@ -672,27 +719,66 @@ __device__ __forceinline__ void inv_row_t(const T* buf, int nvec, int s, int dir
   });
 }
 
-template <typename T, int L, bool FMA, int NV>
-__device__ __forceinline__ void inv_row(const T* buf, int nvec, int s, int dir, int off, const T* f, int taps,
+// The strided branch at a compile-time spacing S (see fwd_row_ct): base = the lowest address of the tap
+// window (tap 0 for DIR > 0, tap L-1 for DIR < 0), every read at an immediate offset.  off is a multiple of V.
+template <typename T, int L, bool FMA, int NV, int S, int DIR, bool FULL>
+__device__ __forceinline__ void inv_row_ct(const T* buf, int nvec, int off, const T* f, T (&acc)[NV][VT<T>::V]) {
+  constexpr int V = VT<T>::V;
+  using vec = typename VT<T>::v;
+  static_assert(S % V == 0 && (L - 1) * S * (int)sizeof(T) < 65536, "aligned reads, 16-bit offsets");
+  const T* const low = buf + off - (DIR > 0 ? 0 : (L - 1) * S);  // uniform part
+  for_vecs<L, NV, FULL>(nvec, [&](int k, int w) {
+    const int t0 = w * V;
+    const unsigned a0 = lds_base(low + t0);
+#pragma unroll
+    for (int i = 0; i < L; ++i) {
+      const vec v = lds_vec_at<vec>(a0 + (unsigned)((DIR > 0 ? i : L - 1 - i) * S * (int)sizeof(T)));
+      vmadd<FMA>(acc[k], v, f[i]);
+      if ((i & 3) == 3) __builtin_amdgcn_sched_barrier(0);  // <= 4 reads in flight (VGPR budget)
+    }
+#pragma unroll
+    for (int e = 0; e < V; ++e) asm volatile("" : "+v"(acc[k][e]));  // pin the sums here (see inv_row_t)
+  });
+}
+
+// ct: as fwd_row -- the spacing (and direction) dispatched once per row, level and branch.
+template <typename T, int L, bool FMA, int NV, bool FULL = false>
+__device__ __forceinline__ void inv_row(const T* buf, int nvec, int s, int dir, int off, const T* f, int taps, int ct,
                                         T (&acc)[NV][VT<T>::V]) {
   constexpr int V = VT<T>::V;
   if constexpr (L > 0) {
     if ((off & (V - 1)) == 0) {
       if (s == 1) {
-        if (dir > 0) return inv_row_t<T, L, FMA, NV, 1, 1>(buf, nvec, s, dir, off, f, taps, acc);
-        return inv_row_t<T, L, FMA, NV, 1, -1>(buf, nvec, s, dir, off, f, taps, acc);
+        if (dir > 0) return inv_row_t<T, L, FMA, NV, 1, 1, FULL>(buf, nvec, s, dir, off, f, taps, acc);
+        return inv_row_t<T, L, FMA, NV, 1, -1, FULL>(buf, nvec, s, dir, off, f, taps, acc);
       }
       if constexpr (V == 4) {
         if (s == 2) {
-          if (dir > 0) return inv_row_t<T, L, FMA, NV, 2, 1>(buf, nvec, s, dir, off, f, taps, acc);
-          return inv_row_t<T, L, FMA, NV, 2, -1>(buf, nvec, s, dir, off, f, taps, acc);
+          if (dir > 0) return inv_row_t<T, L, FMA, NV, 2, 1, FULL>(buf, nvec, s, dir, off, f, taps, acc);
+          return inv_row_t<T, L, FMA, NV, 2, -1, FULL>(buf, nvec, s, dir, off, f, taps, acc);
         }
       }
-      if (dir > 0) return inv_row_t<T, L, FMA, NV, 0, 1>(buf, nvec, s, dir, off, f, taps, acc);
-      return inv_row_t<T, L, FMA, NV, 0, -1>(buf, nvec, s, dir, off, f, taps, acc);
+      if constexpr (L <= 8) {
+        if (ct) {
+          switch (s) {
+#define VW_CASE(n)                                                                                  \
+            case n:                                                                                 \
+              if constexpr (n % V == 0) {                                                           \
+                if (dir > 0) return inv_row_ct<T, L, FMA, NV, n, 1, FULL>(buf, nvec, off, f, acc);  \
+                return inv_row_ct<T, L, FMA, NV, n, -1, FULL>(buf, nvec, off, f, acc);              \
+              }                                                                                     \
+              break;
+            VW_CT_SPACINGS(VW_CASE)
+#undef VW_CASE
+            default: break;
+          }
+        }
+      }
+      if (dir > 0) return inv_row_t<T, L, FMA, NV, 0, 1, FULL>(buf, nvec, s, dir, off, f, taps, acc);
+      return inv_row_t<T, L, FMA, NV, 0, -1, FULL>(buf, nvec, s, dir, off, f, taps, acc);
     }
   }
-  inv_row_t<T, L, FMA, NV, -1, 1>(buf, nvec, s, dir, off, f, taps, acc);
+  inv_row_t<T, L, FMA, NV, -1, 1, FULL>(buf, nvec, s, dir, off, f, taps, acc);
 }
 
 template <typename T, int NV>
@@ -741,9 +827,9 @@ __device__ __forceinline__ void nf_probe(T& z, const T (&v)[V]) {
   for (int e = 0; e < V; ++e) z = nf_step<T>(v[e], z);
 }
 // a row in registers (load_row_regs layout): only the vectors the thread holds (for_vecs)
-template <typename T, int L, int NV, int V>
+template <typename T, int L, int NV, int V, bool FULL = false>
 __device__ __forceinline__ void nf_probe_rows(T& z, const T (&v)[NV][V], int nvec) {
-  for_vecs<L, NV>(nvec, [&](int k, int) { nf_probe<T, V>(z, v[k]); });
+  for_vecs<L, NV, FULL>(nvec, [&](int k, int) { nf_probe<T, V>(z, v[k]); });
 }
 // row b flagged when any lane of any wave saw one (a plain vector store: every writer stores the same 1)
 template <typename T>
@@ -752,16 +838,18 @@ __device__ __forceinline__ void nf_flag_row(int* flag, long long b, T z) {
 }
 
 // NFP: probe the final approximation (nf: the row's accumulator, see nf_probe)
-template <typename T, int L, bool FMA, int NV, bool VALIDATE, bool NFP = false>
+template <typename T, int L, bool FMA, int NV, bool VALIDATE, bool NFP = false, bool FULL = false>
 __device__ __forceinline__ void fwd_level(const FwdArgs<T>& p, const T* X, int nvec, const LevelDesc& lv, T* dout,
                                           T* aout, bool vec_ok, unsigned long long flat0, T (&areg)[NV][VT<T>::V],
                                           T* nf = nullptr) {
   constexpr int V = VT<T>::V;
   const int N = p.N;
-  fwd_row<T, L, FMA, NV>(X, nvec, lv.s, p.lo, p.hi, p.taps, [&](int k, int w, const T (&al)[V], const T (&ah)[V]) {
+  // (the validating form keeps the run-time-stride body: one level body per kernel is enough there)
+  const int ct = VALIDATE ? 0 : p.level_ct;
+  fwd_row<T, L, FMA, NV, FULL>(X, nvec, lv.s, p.lo, p.hi, p.taps, ct, [&](int k, int w, const T (&al)[V], const T (&ah)[V]) {
     const int t0 = w * V;
-    store_vec<VW_FWD_STORE_AUX>(dout, t0, N, vec_ok, ah);
-    if (aout) store_vec<VW_FWD_STORE_AUX>(aout, t0, N, vec_ok, al);
+    store_vec<VW_FWD_STORE_AUX, FULL>(dout, t0, N, vec_ok, ah);
+    if (aout) store_vec<VW_FWD_STORE_AUX, FULL>(aout, t0, N, vec_ok, al);
     if constexpr (VALIDATE) {
       check_out<T>(1, p.bad, flat0, t0, N, ah);
       check_out<T>(1, p.bad, flat0, t0, N, al);
@@ -961,7 +1049,10 @@ __device__ __forceinline__ void wait_vmcnt_rt(int n) {
   }
 }
 
-template <typename T, int L, bool FMA, int NV>
+// FULL: the launch contract above (aligned rows, every slab full) used at compile time -- no per-vector
+// w < nvec mask, no ragged-row test or scalar fallback around the stores (VW_LEVEL_CT; FULL = false keeps
+// the checks of the shared row functions, which can never fire here).
+template <typename T, int L, bool FMA, int NV, bool FULL>
 __global__ void __attribute__((amdgpu_flat_work_group_size(1, NV <= 4 ? 512 : 1024), amdgpu_waves_per_eu(4)))
 k_forward_persist(const FwdArgs<T> p) {
   constexpr int V = VT<T>::V;
@@ -993,10 +1084,10 @@ k_forward_persist(const FwdArgs<T> p) {
       }
       T* dout = p.details + ((size_t)(j - 1) * (size_t)p.B + (size_t)b) * (size_t)N;
       T* aout = (j == p.J) ? p.approx + b * (size_t)N : nullptr;
-      if (p.nf_flag) fwd_level<T, L, FMA, NV, false, true>(p, X, nvec, lv, dout, aout, true, 0ull, areg, &nf);
-      else fwd_level<T, L, FMA, NV, false>(p, X, nvec, lv, dout, aout, true, 0ull, areg);
+      if (p.nf_flag) fwd_level<T, L, FMA, NV, false, true, FULL>(p, X, nvec, lv, dout, aout, true, 0ull, areg, &nf);
+      else fwd_level<T, L, FMA, NV, false, false, FULL>(p, X, nvec, lv, dout, aout, true, 0ull, areg);
       if (j < p.J) {
-        regs_to_level<T, L, NV>(Y, areg, nvec, N, p.lv[j], p.npow2, (const T*)nullptr);
+        regs_to_level<T, L, NV, FULL>(Y, areg, nvec, N, p.lv[j], p.npow2, (const T*)nullptr);
         T* t = X; X = Y; Y = t;
       }
     }
@@ -1109,9 +1200,9 @@ __global__ void VW_FUSED_BOUNDS(NV, VW_FUSED_W(L, 6)) k_inverse_db(const InvArgs
       load_row_regs<T, NV>(dreg, p.details + (size_t)(j - 2) * plane + b * (size_t)N, N, nvec, vec_ok,
                            p.lv[j - 2].use_d == 0);
     zero_regs<T, NV>(acc);
-    inv_row<T, L, FMA, NV>(X, nvec, lv.s, lv.dir_a, lv.off_a, p.lo, p.taps, acc);
+    inv_row<T, L, FMA, NV>(X, nvec, lv.s, lv.dir_a, lv.off_a, p.lo, p.taps, p.level_ct, acc);
     lds_barrier();  // Y = d_j + halo; every read of X done
-    inv_row<T, L, FMA, NV>(Y, nvec, lv.s, lv.dir_d, lv.off_d, p.hi, p.taps, acc);
+    inv_row<T, L, FMA, NV>(Y, nvec, lv.s, lv.dir_d, lv.off_d, p.hi, p.taps, p.level_ct, acc);
     if (j > 1) regs_to_level<T, L, NV>(X, acc, nvec, N, p.lv[j - 2], 0, (const T*)nullptr);
   }
   for_vecs<L, NV>(nvec, [&](int k, int w) { store_vec<VW_INV_STORE_AUX>(p.y + b * (size_t)N, w * V, N, vec_ok, acc[k]); });
@@ -1125,7 +1216,9 @@ __global__ void VW_FUSED_BOUNDS(NV, VW_FUSED_W(L, 6)) k_inverse_db(const InvArgs
 #ifndef VW_INV_W
 #define VW_INV_W 6  // waves per SIMD of k_inverse_seq (experiment builds: -DVW_INV_W=8 -> 64 VGPRs)
 #endif
-template <typename T, int L, bool FMA, int NV>
+// FULL: aligned rows with every slab full (threads * NV == N / V; host: InvArgs::full) -- the bounds
+// checks of the row transfers and the ragged-row store path are compiled out (VW_LEVEL_CT).
+template <typename T, int L, bool FMA, int NV, bool FULL = false>
 __global__ void VW_FUSED_BOUNDS(NV, VW_FUSED_W(L, VW_INV_W)) k_inverse_seq(const InvArgs<T> p) {
   constexpr int V = VT<T>::V;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -1143,11 +1236,11 @@ __global__ void VW_FUSED_BOUNDS(NV, VW_FUSED_W(L, VW_INV_W)) k_inverse_seq(const
   // VW_FLAG_REF_NONFINITE: probing y flags every row vw_ref.hip must recompute (see there)
   T nf = T(0);
   const bool nfp = p.nf_flag != nullptr;
-  load_row_regs<T, NV>(acc, p.approx + b * (size_t)N, N, nvec, vec_ok, p.approx_zero != 0);
-  load_row_regs<T, NV>(dreg, p.details + (size_t)(p.J - 1) * plane + b * (size_t)N, N, nvec, vec_ok,
+  load_row_regs<T, NV, FULL>(acc, p.approx + b * (size_t)N, N, nvec, vec_ok, p.approx_zero != 0);
+  load_row_regs<T, NV, FULL>(dreg, p.details + (size_t)(p.J - 1) * plane + b * (size_t)N, N, nvec, vec_ok,
                        p.lv[p.J - 1].use_d == 0);
   wait_vmem();
-  regs_to_level<T, L, NV>(R, acc, nvec, N, p.lv[p.J - 1], 0, (const T*)nullptr, p.approx_zero != 0);
+  regs_to_level<T, L, NV, FULL>(R, acc, nvec, N, p.lv[p.J - 1], 0, (const T*)nullptr, p.approx_zero != 0);
 
   for (int j = p.J; j >= 1; --j) {
     const LevelDesc lv = p.lv[j - 1];
@@ -1155,29 +1248,29 @@ __global__ void VW_FUSED_BOUNDS(NV, VW_FUSED_W(L, VW_INV_W)) k_inverse_seq(const
 #if VW_INV_LATE_PF
     // (experiment) d_j issued at the start of level j, live only across the approximation branch
     if (j < p.J)
-      load_row_regs<T, NV>(dreg, p.details + (size_t)(j - 1) * plane + b * (size_t)N, N, nvec, vec_ok,
+      load_row_regs<T, NV, FULL>(dreg, p.details + (size_t)(j - 1) * plane + b * (size_t)N, N, nvec, vec_ok,
                            lv.use_d == 0);
 #endif
     zero_regs<T, NV>(acc);
-    inv_row<T, L, FMA, NV>(R, nvec, lv.s, lv.dir_a, lv.off_a, p.lo, p.taps, acc);
+    inv_row<T, L, FMA, NV, FULL>(R, nvec, lv.s, lv.dir_a, lv.off_a, p.lo, p.taps, p.level_ct, acc);
     lds_barrier();  // every approximation-branch read done
     wait_vmem();    // the d_j prefetch
-    regs_to_level<T, L, NV>(R, dreg, nvec, N, lv, 0, (const T*)nullptr, lv.use_d == 0, p.thr, thr_of(j), p.soft);
+    regs_to_level<T, L, NV, FULL>(R, dreg, nvec, N, lv, 0, (const T*)nullptr, lv.use_d == 0, p.thr, thr_of(j), p.soft);
 #if !VW_INV_LATE_PF
     if (j > 1)
-      load_row_regs<T, NV>(dreg, p.details + (size_t)(j - 2) * plane + b * (size_t)N, N, nvec, vec_ok,
+      load_row_regs<T, NV, FULL>(dreg, p.details + (size_t)(j - 2) * plane + b * (size_t)N, N, nvec, vec_ok,
                            p.lv[j - 2].use_d == 0);
 #endif
     lds_barrier();  // R = d_j + halo
-    inv_row<T, L, FMA, NV>(R, nvec, lv.s, lv.dir_d, lv.off_d, p.hi, p.taps, acc);
+    inv_row<T, L, FMA, NV, FULL>(R, nvec, lv.s, lv.dir_d, lv.off_d, p.hi, p.taps, p.level_ct, acc);
     if (j > 1) {
       lds_barrier();  // every detail-branch read done
-      regs_to_level<T, L, NV>(R, acc, nvec, N, p.lv[j - 2], 0, (const T*)nullptr);
+      regs_to_level<T, L, NV, FULL>(R, acc, nvec, N, p.lv[j - 2], 0, (const T*)nullptr);
     }
   }
-  for_vecs<L, NV>(nvec, [&](int k, int w) { store_vec<VW_INV_STORE_AUX>(p.y + b * (size_t)N, w * V, N, vec_ok, acc[k]); });
+  for_vecs<L, NV, FULL>(nvec, [&](int k, int w) { store_vec<VW_INV_STORE_AUX, FULL>(p.y + b * (size_t)N, w * V, N, vec_ok, acc[k]); });
   if (nfp) {
-    nf_probe_rows<T, L, NV, V>(nf, acc, nvec);
+    nf_probe_rows<T, L, NV, V, FULL>(nf, acc, nvec);
     nf_flag_row<T>(p.nf_flag, b, nf);
   }
 }
@@ -1813,7 +1906,7 @@ __global__ void VW_FUSED_BOUNDS(NV, VW_FUSED_W(L, 6)) k_inverse_blk(const InvArg
     lds_barrier();  // R = a_j + wrap images
     zero_regs<T, NV>(acc);
     if (m) blk_inv_any<T, L, FMA, NV>(R, lo, p.blk_tight, vb, m, flo, acc);
-    else inv_row<T, L, FMA, NV>(R, nvec, lv.s, 1, 0, flo, p.taps, acc);
+    else inv_row<T, L, FMA, NV>(R, nvec, lv.s, 1, 0, flo, p.taps, 0, acc);
     lds_barrier();  // every approximation-branch read done
     wait_vmem();    // the d_j prefetch
     stage_std(dreg, j, lv.use_d == 0 ? 1 : (p.thr ? 2 : 0), thr_of(j));
@@ -1822,7 +1915,7 @@ __global__ void VW_FUSED_BOUNDS(NV, VW_FUSED_W(L, 6)) k_inverse_blk(const InvArg
                            p.lv[j - 2].use_d == 0);
     lds_barrier();  // R = d_j + wrap images
     if (m) blk_inv_any<T, L, FMA, NV>(R, lo, p.blk_tight, vb, m, fhi, acc);
-    else inv_row<T, L, FMA, NV>(R, nvec, lv.s, 1, 0, fhi, p.taps, acc);
+    else inv_row<T, L, FMA, NV>(R, nvec, lv.s, 1, 0, fhi, p.taps, 0, acc);
     if (j > 1) {
       lds_barrier();  // every detail-branch read done
 #pragma unroll

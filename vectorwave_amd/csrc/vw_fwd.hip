@@ -64,9 +64,9 @@ template hipError_t launch_forward_blk<VW_T>(const FwdArgs<VW_T>&, int, int, boo
 
 // Persistent forward (k_forward_persist): as many workgroups as are resident at once, each walking
 // signals blockIdx.x + k*gridDim.x.  The resident count comes from the occupancy API (LDS-bound).
-template <typename T, int L, bool FMA, int NV>
+template <typename T, int L, bool FMA, int NV, bool FULL>
 static hipError_t run_forward_persist(const FwdArgs<T>& a, int threads, int lds, hipStream_t st) {
-  auto k = k_forward_persist<T, L, FMA, NV>;
+  auto k = k_forward_persist<T, L, FMA, NV, FULL>;
   static LdsOnce configured;
   hipError_t e = set_lds(k, lds, &configured);
   if (e != hipSuccess) return e;
@@ -93,7 +93,9 @@ static hipError_t run_forward_persist(const FwdArgs<T>& a, int threads, int lds,
 template <typename T, int L, bool FMA>
 static hipError_t run_forward_persist_nv(const FwdArgs<T>& a, int threads, int lds, int nv, hipStream_t st) {
   (void)nv;  // NV = 4 only (host contract)
-  return run_forward_persist<T, L, FMA, 4>(a, threads, lds, st);
+  // the contract makes every slab full: the full-slab form unless VW_LEVEL_CT=0 asks for the checked one
+  return a.level_ct ? run_forward_persist<T, L, FMA, 4, true>(a, threads, lds, st)
+                    : run_forward_persist<T, L, FMA, 4, false>(a, threads, lds, st);
 }
 
 template <typename T>

@@ -56,6 +56,8 @@ struct FwdArgs {
   int vec_io;
   int unrolled;         // 1: the tap-unrolled kernel may run (aligned rows, full slabs; vw_capi fused_plan)
   int dma_nt;           // k_forward_persist: non-temporal LDS-DMA of the signal rows
+  int level_ct;         // 1: strided levels of short filters dispatch to compile-time-stride bodies, and
+                        // k_forward_persist runs its full-slab form (VW_LEVEL_CT; vw_device.h fwd_row_ct)
   int validate;         // 1: non-finite check on input and outputs (atomicMin into *bad)
   int rev;              // 1: workgroup g owns signal B-1-g (walk order, see vw_capi.cpp walk_reverse)
   unsigned long long* bad;
@@ -85,6 +87,8 @@ struct InvArgs {
   int vec_io;
   int pair;             // 1: sum += (h*a + g*d) per tap (MODWTTransform.inverse, ZERO multi-level)
   int unrolled;
+  int level_ct;         // 1: compile-time-stride level bodies (VW_LEVEL_CT; vw_device.h inv_row_ct)
+  int full;             // 1: aligned rows, threads * NV == N / V: k_inverse_seq's full-slab form may run
   int db;               // sequential sum: 1 = two LDS buffers (k_inverse_db), 0 = one (k_inverse_seq)
   int blk;              // 1: register-blocked PERIODIC inverse (k_inverse_blk), padded LDS layouts
   int approx_zero;

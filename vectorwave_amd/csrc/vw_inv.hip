@@ -7,15 +7,21 @@ namespace vw {
 template <typename T, int L, bool FMA, int NV>
 static hipError_t run_inverse_fused_nv(const InvArgs<T>& a, int threads, int lds, hipStream_t st) {
   // pairwise sums: k_inverse_fused; sequential sums: two LDS buffers (k_inverse_db) or one (k_inverse_seq)
-  static LdsOnce configured_pair, configured_seq, configured_db, configured_blk;
+  static LdsOnce configured_pair, configured_seq, configured_db, configured_blk, configured_full;
   // register-blocked PERIODIC (host contract; never with NV = 2)
   const bool blk = L > 0 && NV != 2 && a.blk && !a.pair && !a.db;
   auto k = a.pair ? k_inverse_fused<T, L, FMA, NV> : a.db ? k_inverse_db<T, L, FMA, NV> : k_inverse_seq<T, L, FMA, NV>;
   if constexpr (NV != 2) {
     if (blk) k = k_inverse_blk<T, (L > 0 ? L : 2), FMA, NV>;
   }
+  // full-slab form of the one-buffer sequential kernel (host: InvArgs::full), short filters at NV = 4
+  bool full = false;
+  if constexpr (NV == 4 && L > 0 && L <= 8) {
+    full = a.full && !a.pair && !a.db && !blk;
+    if (full) k = k_inverse_seq<T, L, FMA, NV, true>;
+  }
   hipError_t e = set_lds(k, lds, a.pair ? &configured_pair : a.db ? &configured_db
-                                 : blk ? &configured_blk : &configured_seq);
+                                 : blk ? &configured_blk : full ? &configured_full : &configured_seq);
   if (e != hipSuccess) return e;
   hipLaunchKernelGGL(k, dim3((unsigned)a.B), dim3(threads), lds, st, a);
   return hipGetLastError();
