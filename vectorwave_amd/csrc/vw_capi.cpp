@@ -1327,8 +1327,9 @@ static vw_status forward_impl(vw_ctx* c, const T* x, int64_t B, int64_t N, int64
     // (NV = 8, 1024-thread workgroups: with its taps from the kernel arguments (round 4, 99 VGPRs, no
     // spills) the blocked forward beats the fused one at sym8 N = 16384: 5.27-5.29 -> 4.76 ms,
     // profiles/r04/ab_blk_fwd8_ktaps_sym8.log; VW_BLK_FWD8=0 restores the fused kernel)
-    if (tu.blk > 0 && L >= tu.blk && a.unrolled && !validate && !hist && (int64_t)threads * nv == nvec &&
-        (nv == 4 || (nv == 8 && tu.blk_fwd8))) {
+    // (listed tap counts only: launch_forward_blk has no runtime-L form)
+    if (tu.blk > 0 && L >= tu.blk && has_unrolled_taps(L) && a.unrolled && !validate && !hist &&
+        (int64_t)threads * nv == nvec && (nv == 4 || (nv == 8 && tu.blk_fwd8))) {
       bool okb = true;
       int hlv = 0;
       for (int j = 0; j < J; ++j) {
@@ -1602,7 +1603,8 @@ static vw_status inverse_impl(vw_ctx* c, const T* details, const T* approx, int6
   // profiles/r02/ab_small_batch.log, ab_inv_buf_1024_768.log); VW_INV_BUF=1|2 overrides.
   // Long PERIODIC filters (L >= VW_BLK) keep the register-blocked single-buffer kernel (k_inverse_blk
   // needs !db) at small batches too: its NV+L-1 LDS reads per branch outweigh the shorter barrier chain.
-  const bool blk_pref = tu.blk > 0 && L >= tu.blk && boundary == VW_PERIODIC;
+  // Only listed tap counts have a k_inverse_blk: other lengths follow the short filters' policy.
+  const bool blk_pref = tu.blk > 0 && L >= tu.blk && has_unrolled_taps(L) && boundary == VW_PERIODIC;
   bool db = !pair && (tu.inv_buf ? tu.inv_buf == 2 : (B <= 2LL * c->cus && !blk_pref));
   bool fused = false, fit = false;
   const bool inv_io = (N % V == 0) && aligned16(details) && aligned16(approx) && aligned16(y);
@@ -1628,8 +1630,8 @@ static vw_status inverse_impl(vw_ctx* c, const T* details, const T* approx, int6
     a.level_ct = tu.level_ct;
     a.full = tu.level_ct && a.unrolled && (int64_t)threads * nv == nvec;
     // register-blocked PERIODIC inverse for long filters (vw_device.h k_inverse_blk)
-    if (tu.blk > 0 && L >= tu.blk && nv != 2 && !pair && !db && boundary == VW_PERIODIC && a.unrolled &&
-        (int64_t)threads * nv == nvec) {
+    if (tu.blk > 0 && L >= tu.blk && has_unrolled_taps(L) && nv != 2 && !pair && !db && boundary == VW_PERIODIC &&
+        a.unrolled && (int64_t)threads * nv == nvec) {
       bool okb = true;
       int64_t buf = 0;
       const int mJ = std::max(1, lv[J - 1].s / V);
