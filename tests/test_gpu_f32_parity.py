@@ -171,7 +171,7 @@ def test_partial_reconstruction(engine, w, boundary, tiled, n):
 @pytest.mark.parametrize("pad", [1, 2, 4])   # fp32: 1, 2 break the row alignment; fp64: 1 does
 def test_forward_leading_dimension(engine, dt, pad):
     """vw_modwt_forward_* on rows of a wider buffer (ldx > N) against the restatement.  Every kernel the call can
-    reach takes the row alignment from the host (vec_io / io_aligned / deep's lda test in vw_capi.cpp all include
+    reach takes the row alignment from the host (vec_io / io_aligned / deep's lda test in vw_plan.cpp all include
     ldx % V == 0), so ldx % V != 0 runs the scalar row loads."""
     w, B, N, J = Daubechies.DB4, 5, 1024, 4
     tdt = torch.float32 if dt == "f32" else torch.float64

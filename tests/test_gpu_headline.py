@@ -2,7 +2,7 @@
 
 BASELINE.json configs[1]: db4, J = 6, 4096 x 4096 fp64, PERIODIC, forward + inverse, the default kernel
 policy -- at B = 4096 > 2 signals per CU that is k_forward_persist (512 resident workgroups, each walking
-8 signals with the next row arriving by LDS-DMA) and k_inverse_seq (vw_capi.cpp inverse_impl policy).
+8 signals with the next row arriving by LDS-DMA) and k_inverse_seq (vw_plan.cpp plan_inverse_fused policy).
 Rows are picked across the batch and across resident workgroups: b and b + 512 are walked by the same
 persistent workgroup, b and b + 1 by neighbours on different CUs / XCDs.
 

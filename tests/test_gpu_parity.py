@@ -410,7 +410,7 @@ def test_tiled_path_bit_exact(engine):
 
 @pytest.mark.parametrize("tile", [128, 2048])
 def test_multilevel_tiles_bit_exact(engine, tile):
-    # long PERIODIC signals run groups of levels per tile (vw_capi.cpp level_groups): odd N (scalar
+    # long PERIODIC signals run groups of levels per tile (vw_plan.cpp level_groups): odd N (scalar
     # I/O), N not a multiple of the tile, tiles shorter than the reach (wraps through the halo), and
     # the SWT denoise thresholds applied on the detail loads; EXACT mode is bit-exact
     with engine.options(VW_FORCE_TILED=1, VW_MULTI_TILE=tile):

@@ -1,11 +1,12 @@
 // vw_capi.cpp -- C ABI of the MI355X MODWT/SWT engine (include/vectorwave_amd.h).
 //
-// Host-side bookkeeping restated from the reference (level cap, L_j guard, symmetric alignment
-// tables, FFT-switch region, status mapping), then one fused HIP launch per transform
-// (vw_kernels.hip), or one tiled launch per level for signals longer than LDS holds.
+// Contexts, streams, graphs, pipelines, staging, argument checks and status mapping; the transforms
+// execute the plans of vw_plan.cpp (which kernels, launch shapes, LDS layouts, buffers, reservations):
+// one fused HIP launch per transform, or the per-level steps for signals longer than LDS holds.
 #include "../../include/vectorwave_amd.h"
 #include "vw_internal.h"
 #include "vw_deep.h"
+#include "vw_plan.h"
 
 #include <algorithm>
 #include <cmath>
@@ -62,124 +63,6 @@ struct TimedLaunch {
   hipEvent_t start, stop;
   bool graph_owned = false;  // recorded inside a captured graph: its events live as long as the graph
 };
-
-// Tuning switches (A/B experiments, tools/ab_*.sh), read from the environment ONCE per context at
-// vw_ctx_create -- never per call: a transform call does no getenv.  Defaults are the measured best.
-struct Tuning {
-  int nv = 4;              // VW_NV: vectors per thread of the fused kernels (4 or 8)
-  bool fwd_persist = true; // VW_FWD_PERSIST=0: no persistent forward
-  int fwd_buf = 0;         // VW_FWD_BUF=1|2: force one / two forward level buffers (0 = policy)
-  bool force_tiled = false;// VW_FORCE_TILED: per-level path even when the fused kernels fit
-  int fwd_rev = 0, inv_rev = 0;  // VW_FWD_REV / VW_INV_REV: reverse workgroup -> signal walk
-  int dma_nt = -1;               // VW_DMA_NT=0|1: LDS-DMA of signal rows non-temporal; -1 = policy (see forward_impl)
-  int fwd_tile = 0;        // VW_FWD_TILE: per-level forward tile (0 = default)
-  bool multi = true;       // VW_MULTI=0: one launch per level on the long-signal path
-  int multi_div = 4;       // VW_MULTI_DIV: reach bound of a level group = tile / div
-  int multi_tile = 0;      // VW_MULTI_TILE: multi-level tile (0 = 16 KiB of samples)
-  int inv_buf = 0;         // VW_INV_BUF=2: two-buffer sequential inverse (k_inverse_db)
-  int inv_tile = 0;        // VW_INV_TILE: per-level inverse tile (0 = 1024)
-  int multi_rblk = 1;      // VW_MULTI_RBLK: register-blocked taps in k_inverse_multi
-  int multi_pf = 1;        // VW_MULTI_PF: k_inverse_multi prefetches the next detail tile
-  int multi_pad = 1;       // VW_MULTI_PAD: k_inverse_multi's padded LDS layout at register-blocked levels
-  int multi_inv_tile = 0;  // VW_MULTI_INV_TILE: k_inverse_multi's tile (0 = VW_MULTI_TILE's)
-  int multi_ni = 4;        // VW_MULTI_NI: k_inverse_multi's output vectors per thread -- 4 (fp64, on the largest tile
-                           // whose levels fit 256 threads) or 8; db8-stream inverse 9.19-9.33 -> 8.75-8.80 ms
-                           // (profiles/r05/ab_db8_inverse_multi_ni4.log)
-  bool no_sweep = false;   // VW_NO_SWEEP: no column sweeps for deep levels
-  int sweep_qc = kSweepChunk;  // VW_SWEEP_QC: q-chunk per sweep thread
-  int unroll_max = kMaxTaps;   // VW_UNROLL_MAX: longest filter that runs the tap-unrolled fused kernels
-  int blk = 10;                // VW_BLK: shortest filter that runs the register-blocked PERIODIC kernels (0 = off)
-                               // (measured on MI355X, db8 J=10 2^20 blocks: no faster than the sweeps yet)
-  bool deep = true;             // VW_DEEP=0|1: streaming deep-level forward (vw_deep.hip) off / on
-  bool deep_inv = false;       // VW_DEEP_INV=1 (or VW_DEEP=1): the deep inverse too -- measured slower than
-                               // the column sweeps on db8-stream (profiles/r03/ab_deep_db8_stream.log)
-  int deep_lds = 80;           // VW_DEEP_LDS: LDS budget of one deep group, KiB (80 = two workgroups per CU)
-  int deep_waves = 4;          // VW_DEEP_WAVES: target deep workgroups per CU when choosing segments
-  int deep_pf_fwd = 1;         // VW_DEEP_PF_FWD / VW_DEEP_PF_INV: tiles of DMA-fed input in flight
-  int deep_pf_inv = 1;
-  int fwd_nv = 0;              // VW_FWD_NV / VW_INV_NV = 2: 1024-thread fused kernels with 2 vectors per
-  int inv_nv = 0;              // thread (L <= 8, unrolled); 0 = policy
-  int sweep2 = 3;              // VW_SWEEP2: deep inverse column-sweep levels chained per launch, up to 3 (2 = pairs only,
-                               // 0 = one sweep per level)
-  int sweep2_ka = 8;           // VW_SWEEP2_KA: stage-A outputs per thread and step (8 or 16)
-  int sweep2_uc = 2048;        // VW_SWEEP2_UC: u positions per workgroup chunk (512 / 1024 / 2048: 9.68 / 9.50 / 9.33 ms db8 inverse)
-  int sweep2_r = 0;            // VW_SWEEP2_R=32: 32-residue groups even where h allows 64 (0 = widest)
-  int sweep2_minb = 64;        // VW_SWEEP2_MINB: blocks a residue class needs for the chained sweeps
-  int blk_fwd8 = 1;            // VW_BLK_FWD8=0: fused forward instead of the register-blocked one at NV = 8
-  int ref_grid = 0;            // VW_REF_GRID: workgroups of the REF_NONFINITE fix-up launch (0 = 2 per CU)
-  int level_ct = 1;            // VW_LEVEL_CT=0: run-time level strides and bounds-checked slabs in the fused kernels of
-                               // short filters (L <= 8), as before (profiles/r07/ab_db4_level_ct.log)
-  int mfma = 0;                // VW_MFMA=1|2|3: fp32 FMA PERIODIC forward (1) / inverse (2) / both (3) on the matrix
-                               // cores (vw_mfma.hip)
-};
-
-// One switch of the Tuning struct by its environment name; value < 0 = the default.  Returns false
-// for an unknown name.
-static bool set_tuning(Tuning& t, const char* key, int v) {
-  const Tuning d;
-  const std::string k(key);
-  if (k == "VW_NV") t.nv = v < 0 ? d.nv : v <= 4 ? 4 : 8;
-  else if (k == "VW_FWD_PERSIST") t.fwd_persist = v < 0 ? d.fwd_persist : v != 0;
-  else if (k == "VW_FWD_BUF") t.fwd_buf = v < 0 ? d.fwd_buf : v;
-  else if (k == "VW_FORCE_TILED") t.force_tiled = v > 0;
-  else if (k == "VW_FWD_REV") t.fwd_rev = v < 0 ? 0 : v;
-  else if (k == "VW_INV_REV") t.inv_rev = v < 0 ? 0 : v;
-  else if (k == "VW_DMA_NT") t.dma_nt = v < 0 ? d.dma_nt : v;
-  else if (k == "VW_FWD_TILE") t.fwd_tile = v < 0 ? 0 : v;
-  else if (k == "VW_MULTI") t.multi = v < 0 ? d.multi : v != 0;
-  else if (k == "VW_MULTI_DIV") t.multi_div = v <= 0 ? d.multi_div : v;
-  else if (k == "VW_MULTI_TILE") t.multi_tile = v < 0 ? 0 : v;
-  else if (k == "VW_INV_BUF") t.inv_buf = v < 0 ? 0 : v;  // 0 = policy
-  else if (k == "VW_INV_TILE") t.inv_tile = v < 0 ? 0 : v;
-  else if (k == "VW_MULTI_RBLK") t.multi_rblk = v < 0 ? d.multi_rblk : v;
-  else if (k == "VW_MULTI_PF") t.multi_pf = v < 0 ? d.multi_pf : v;
-  else if (k == "VW_MULTI_PAD") t.multi_pad = v < 0 ? d.multi_pad : v;
-  else if (k == "VW_MULTI_INV_TILE") t.multi_inv_tile = v < 0 ? 0 : v;
-  else if (k == "VW_MULTI_NI") t.multi_ni = v < 0 ? d.multi_ni : v == 4 ? 4 : 8;
-  else if (k == "VW_NO_SWEEP") t.no_sweep = v > 0;
-  else if (k == "VW_SWEEP_QC") t.sweep_qc = v >= 16 ? v : d.sweep_qc;
-  else if (k == "VW_UNROLL_MAX") t.unroll_max = v < 0 ? d.unroll_max : v;
-  else if (k == "VW_BLK") t.blk = v < 0 ? d.blk : v;
-  else if (k == "VW_DEEP") { t.deep = v < 0 ? d.deep : v != 0; t.deep_inv = v < 0 ? d.deep_inv : v != 0; }
-  else if (k == "VW_DEEP_INV") t.deep_inv = v < 0 ? d.deep_inv : v != 0;
-  else if (k == "VW_DEEP_LDS") t.deep_lds = v <= 0 ? d.deep_lds : v;
-  else if (k == "VW_DEEP_WAVES") t.deep_waves = v <= 0 ? d.deep_waves : v;
-  else if (k == "VW_DEEP_PF_FWD") t.deep_pf_fwd = v <= 0 ? d.deep_pf_fwd : std::min(v, 16);
-  else if (k == "VW_DEEP_PF_INV") t.deep_pf_inv = v <= 0 ? d.deep_pf_inv : std::min(v, 16);
-  else if (k == "VW_FWD_NV") t.fwd_nv = v < 0 ? d.fwd_nv : v;
-  else if (k == "VW_INV_NV") t.inv_nv = v < 0 ? d.inv_nv : v;
-  else if (k == "VW_SWEEP2") t.sweep2 = v < 0 ? d.sweep2 : v;
-  else if (k == "VW_SWEEP2_KA") t.sweep2_ka = v == 16 ? 16 : v == 8 ? 8 : d.sweep2_ka;
-  else if (k == "VW_SWEEP2_UC") t.sweep2_uc = v >= 32 ? v : d.sweep2_uc;
-  else if (k == "VW_SWEEP2_R") t.sweep2_r = v == 32 ? 32 : 0;
-  else if (k == "VW_SWEEP2_MINB") t.sweep2_minb = v < 0 ? d.sweep2_minb : v;
-  else if (k == "VW_BLK_FWD8") t.blk_fwd8 = v < 0 ? d.blk_fwd8 : v;
-  else if (k == "VW_LEVEL_CT") t.level_ct = v < 0 ? d.level_ct : v != 0;
-  else if (k == "VW_MFMA") t.mfma = v < 0 ? d.mfma : v;
-  else if (k == "VW_REF_GRID") t.ref_grid = v < 0 ? d.ref_grid : v;
-  else return false;
-  return true;
-}
-
-static const char* const kTuningKeys[] = {
-    "VW_NV", "VW_FWD_PERSIST", "VW_FWD_BUF", "VW_FORCE_TILED", "VW_FWD_REV", "VW_INV_REV",
-    "VW_FWD_TILE", "VW_MULTI", "VW_MULTI_DIV", "VW_MULTI_TILE", "VW_INV_BUF", "VW_INV_TILE", "VW_MULTI_RBLK", "VW_MULTI_PF", "VW_MULTI_PAD", "VW_MULTI_INV_TILE", "VW_NO_SWEEP", "VW_SWEEP_QC",
-    "VW_UNROLL_MAX", "VW_BLK", "VW_FWD_NV",
-    "VW_INV_NV", "VW_DEEP", "VW_DEEP_INV", "VW_DEEP_LDS", "VW_DEEP_WAVES", "VW_DEEP_PF_FWD", "VW_DEEP_PF_INV",
-    "VW_SWEEP2", "VW_SWEEP2_KA", "VW_SWEEP2_UC", "VW_SWEEP2_R", "VW_SWEEP2_MINB", "VW_BLK_FWD8",
-    "VW_DMA_NT", "VW_MULTI_NI", "VW_MFMA", "VW_REF_GRID", "VW_LEVEL_CT"};
-
-static Tuning read_tuning() {
-  Tuning t;
-  for (const char* k : kTuningKeys) {
-    const char* e = getenv(k);
-    if (!e) continue;
-    // presence-style switches (VW_FORCE_TILED, VW_NO_SWEEP) are on when set to anything but "0"
-    const int v = (*e == '\0') ? 1 : atoi(e);
-    set_tuning(t, k, v);
-  }
-  return t;
-}
 
 struct vw_graph;
 struct vw_ctx;
@@ -373,96 +256,11 @@ static vw_status ensure_nf(vw_ctx* c, int64_t B) {
 }
 
 static inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
-static inline int64_t round_up(int64_t v, int64_t a) { return (v + a - 1) / a * a; }
 
 // ------------------------------------------------------------------------------------------------
-// Bookkeeping restated from the reference.
-
-// MultiLevelMODWTTransform.calculateMaxLevels  core/modwt/MultiLevelMODWTTransform.java:455-501
-extern "C" int vw_max_levels(int64_t N, int L) {
-  if (L <= 0 || N <= L) return 0;
-  int max_level = 1;
-  const long long lm1 = L - 1;
-  while (max_level < 10) {
-    const long long scaled = lm1 * (1LL << (max_level - 1)) + 1LL;
-    if (scaled > N) break;
-    max_level++;
-  }
-  return max_level - 1;
-}
-
-extern "C" int64_t vw_upsampled_length(int L, int level) {
-  const int64_t up = (level <= 1) ? 1 : ((int64_t)1 << (level - 1));
-  return (int64_t)(L - 1) * up + 1;
-}
-
-// SymmetricAlignmentStrategy.decide  core/modwt/SymmetricAlignmentStrategy.java:43-117
-static void sym_decide(int wid, int L, int level, int* ap, int* dh, int* dp, int* dg) {
-  int detailPlus = 1, deltaG = 0, deltaH = 0;
-  const bool isHaar = L <= 2;
-  int approxPlus = isHaar ? 1 : 0;
-  if (isHaar) {
-    deltaG = 0;
-    deltaH = (level <= 1) ? 0 : -1;
-  } else if (wid == VW_WID_DB6) {
-    deltaH = (level <= 1) ? 0 : -1;
-    deltaG = (level >= 3) ? 1 : 0;
-  } else if (wid == VW_WID_DB8) {
-    deltaH = (level <= 1) ? 0 : 1;
-    deltaG = (level >= 2) ? 1 : 0;
-  } else if (wid == VW_WID_SYM4) {
-    approxPlus = 1; detailPlus = 0; deltaH = 0; deltaG = 0;
-  } else if (wid == VW_WID_SYM8) {
-    if (level <= 1) { deltaH = 0; deltaG = 0; }
-    else if (level == 2) { deltaH = 1; deltaG = 0; }
-    else { deltaH = 1; deltaG = 1; }
-  } else if (wid == VW_WID_COIF2) {
-    approxPlus = 1; deltaH = (level <= 1) ? 0 : 1; detailPlus = 0; deltaG = 0;
-  } else if (wid == VW_WID_COIF3) {
-    detailPlus = 0;
-    if (level <= 1) { deltaH = 0; deltaG = 0; } else { deltaH = -1; deltaG = 1; }
-  } else if (L >= 12) {
-    if (level <= 1) { deltaH = 0; deltaG = 0; }
-    else { const bool even = level % 2 == 0; deltaH = even ? 0 : -1; deltaG = even ? 0 : -1; }
-  } else {
-    if (level <= 1) { deltaH = 0; deltaG = 0; } else { deltaH = -1; deltaG = 0; }
-  }
-  *ap = approxPlus; *dh = deltaH; *dp = detailPlus; *dg = deltaG;
-}
-
-// MultiLevelMODWTTransform.computeTauJ  core/modwt/MultiLevelMODWTTransform.java:795-806
-static int compute_tau(int base_len, int level) {
-  const int lm1 = base_len - 1;
-  if (level <= 1) return std::max(0, lm1 / 2);
-  const long long up = 1LL << (level - 1);
-  const long long Lj = (long long)lm1 * up + 1LL;
-  const long long tau = (Lj - 1LL) / 2LL;
-  if (tau < 0) return 0;
-  if (tau > 2147483647LL) return 2147483647;
-  return (int)tau;
-}
-
-static int next_pow2(int64_t n) {
-  int64_t p = 1;
-  while (p < n) p <<= 1;
-  return (int)p;
-}
-
-static bool is_pow2(int64_t n) { return n > 0 && (n & (n - 1)) == 0; }
-
-// Level-j input index range read by a branch (dir, off) for outputs t in [0, tmax].
-static void branch_extent(int N, int tmax, int L, int s, int dir, int off, int* hl, int* hr) {
-  const long long reach = (long long)(L - 1) * s;
-  long long mn, mx;
-  if (dir > 0) { mn = off; mx = (long long)tmax + reach + off; }
-  else { mn = (long long)off - reach; mx = (long long)tmax + off; }
-  *hl = (int)std::max<long long>(*hl, -mn);
-  *hr = (int)std::max<long long>(*hr, mx - (N - 1));
-}
-
-template <typename T> static constexpr int vec_width() { return 16 / (int)sizeof(T); }
-
-static bool aligned16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
+// Bookkeeping restated from the reference (vw_plan.cpp).
+extern "C" int vw_max_levels(int64_t N, int L) { return max_levels(N, L); }
+extern "C" int64_t vw_upsampled_length(int L, int level) { return upsampled_length(L, level); }
 
 // ------------------------------------------------------------------------------------------------
 // Context
@@ -982,193 +780,12 @@ static vw_status report_bad(unsigned long long bad, int64_t N) {
               (long long)(flat / (unsigned long long)N) + (long long)t_signal_base);
 }
 
-// Plan of a fused launch: threads, vectors per thread (4 or 8), LDS bytes.  NV = 4 keeps the
-// per-thread register arrays small (no spills); NV = 8 reaches N = 1024 * 8 * V.  The workgroup is
-// ceil(nvec / NV) threads (not rounded to a wave): thread `tid` owns vectors tid + k*threads, and
-// the unrolled kernels rely on slabs 0..NV-2 being full, `fit` = (NV-1)*threads <= nvec (else the
-// runtime-L kernel with a bounds check per vector runs).
-static bool fused_plan(const Tuning& tu, int64_t N, int V, int elem, int64_t lds_elems_extra, int* threads, int* nv,
-                       int* lds, bool* fit, int nv_req = 0) {
-  const int64_t nvec = (N + V - 1) / V;
-  int want = tu.nv;
-  if ((nvec + want - 1) / want > 512) want = 8;  // NV = 4 kernels are bounded to 512 threads (VW_FUSED_BOUNDS)
-  // NV = 2: 1024 threads at most, every slab full (the unrolled kernels' contract)
-  if (nv_req == 2 && nvec % 2 == 0 && nvec / 2 <= kMaxThreads) want = 2;
-  const int64_t th = (nvec + want - 1) / want;
-  if (th > kMaxThreads) return false;
-  const int64_t bytes = lds_elems_extra * elem;
-  if (bytes > kLdsBytes) return false;
-  *nv = want;
-  *threads = (int)th;
-  *lds = (int)bytes;
-  *fit = (int64_t)(want - 1) * th <= nvec;
-  return true;
-}
-
-
-// Owner-written halo of one level (vw_device.h halo_images): the affine images of an element and
-// the vector bands that have them; `own` only when every band lies in the slab that checks it.
-static void set_halo_images(LevelDesc& d, int64_t N, int64_t npow2, int V, int threads, int nv) {
-  int64_t s_el = 0, e_el = N;
-  d.il_a = 0; d.il_b = 1; d.ir_a = 0; d.ir_b = -1;  // no images
-  switch (d.mode) {
-    case kHaloPeriodic:
-      d.il_a = 1; d.il_b = (int)-N; d.ir_a = 1; d.ir_b = (int)N;
-      s_el = d.hr; e_el = N - d.hl;
-      break;
-    case kHaloSymmetric:
-      d.il_a = -1; d.il_b = -1; d.ir_a = -1; d.ir_b = (int)(2 * N - 1);
-      s_el = d.hl; e_el = N - d.hr;
-      break;
-    case kHaloFftPad:
-      d.il_a = 1; d.il_b = (int)-npow2;
-      e_el = npow2 - d.hl;
-      break;
-    default:
-      break;
-  }
-  e_el = std::min<int64_t>(std::max<int64_t>(e_el, 0), N);
-  d.vs = (int)((s_el + V - 1) / V);
-  d.ve = (int)(e_el / V);
-  d.own = (d.hl <= N && d.hr <= N && d.vs <= threads && (int64_t)d.ve >= (int64_t)(nv - 1) * threads) ? 1 : 0;
-}
-
-// Level groups of the per-level path (vw_device.h k_forward_multi / k_inverse_multi): from level 1
-// up, consecutive PERIODIC levels run as one multi-level tile launch while their combined reach
-// sum((L-1)*s_j) stays within a quarter of the tile (the redundant arithmetic).  groups[j-1] = size
-// of the group starting at level j (0 inside a group, 1 = the per-level kernels).  VW_MULTI=0
-// disables; VW_MULTI_TILE / VW_MULTI_DIV tune tile and reach bound.
-template <typename T>
-static int multi_tile(const Tuning& tu) {
-  constexpr int V = vec_width<T>();
-  const int v = tu.multi_tile ? tu.multi_tile : (int)(16384 / sizeof(T));
-  return v >= 64 * V ? v / V * V : 64 * V;
-}
-
-static std::vector<int> level_groups(const Tuning& tu, const std::vector<LevelDesc>& lv, int J, int L, int V, int tile,
-                                     bool ok) {
-  std::vector<int> g(J, 1);
-  if (!ok || !tu.multi) return g;
-  const int64_t cap = tile / tu.multi_div;
-  for (int j = 1; j <= J;) {
-    int n = 0;
-    int64_t ext = 0;
-    while (j + n <= J && n < kMaxGroup && lv[j + n - 1].mode == kHaloPeriodic) {
-      const int64_t e2 = ext + round_up((int64_t)(L - 1) * lv[j + n - 1].s, V);
-      if (e2 > cap) break;
-      ext = e2;
-      ++n;
-    }
-    if (n >= 2) {
-      g[j - 1] = n;
-      for (int k = 1; k < n; ++k) g[j - 1 + k] = 0;
-      j += n;
-    } else {
-      ++j;
-    }
-  }
-  return g;
-}
-
-// Level group of the chained column sweeps (vw_device.h k_inverse_sweep2 / k_inverse_sweep3): inverse levels
-// j .. j-levels+1 (spacings G*h .. h, G = 2 / 4), all column-sweep levels outside the multi-level tile
-// groups, PERIODIC / dir +1 / offset 0.  Picks KA (outputs per thread and step) and R (residues per
-// group, 64 or 32 = h's alignment) under the kernels' rules: a block of G*KA positions covers the
-// reach of the levels below the top (L-1 per level, in the bottom level's positions: 1 / 2 steps), the
-// LDS rings (1 / 2 of 3 blocks x R) fit, one wrap mod N at most, and residue classes of >= 64 blocks.
-template <typename T>
-static bool sweepg_plan(const Tuning& tu, const std::vector<LevelDesc>& lv, int j, int levels, int L, int64_t N,
-                        const std::vector<char>& in_group, const std::vector<int>& start_of, int* ka_out, int* r_out) {
-  if (levels < 2 || levels > 3 || j < levels) return false;
-  const int G = levels == 2 ? 2 : 4;
-  const int64_t h = lv[j - levels].s;
-  if (h < kSweepMinS || h % 32 != 0 || lv[j - 1].s != G * h) return false;
-  for (int k = j - levels + 1; k <= j; ++k) {
-    const LevelDesc& d = lv[k - 1];
-    if (d.mode != kHaloPeriodic || d.dir_a != 1 || d.dir_d != 1 || d.off_a != 0 || d.off_d != 0) return false;
-    if (k < j && (in_group[k] || start_of[k] != 0)) return false;
-  }
-  const int R = (h % 64 == 0 && tu.sweep2_r != 32) ? 64 : 32;
-  const int kmin = (levels == 2 ? 1 : 2) * (L - 1);
-  for (int ka : {L <= 17 ? tu.sweep2_ka : 16, 16}) {
-    for (int r : {R, 32}) {
-      const int64_t kb = (int64_t)G * ka;
-      const int64_t lds = (levels == 2 ? 1 : 2) * 3 * kb * r * (int64_t)sizeof(T);
-      if (kb < kmin || lds > kLdsBytes || h % r != 0) continue;
-      if (N % (G * h) != 0 || (2 * kb + 2 * L) * G * h > N) continue;
-      // short residue classes: the pipeline's fill (2 / 4 steps per chunk) is not amortised -- on sym8
-      // 16384-sample signals through the tiled path a triple ran 21.2 ms vs 12.3 for pairs
-      // (profiles/r03/ab_sweepg_short.log); such levels keep one sweep each
-      if (N / h < (int64_t)tu.sweep2_minb * kb) continue;
-      *ka_out = ka;
-      *r_out = r;
-      return true;
-    }
-  }
-  return false;
-}
-
-// Streaming deep group (vw_deep.hip): PERIODIC levels jlo..jhi of the per-level path in one launch.
-// Needs level jlo's spacing P to divide N and hold C = 64 bytes of residues; every ring of the group
-// within the LDS budget.  Ring capacities: DMA-fed rings hold their history + two tiles (the next
-// tile lands while the current one computes), multiples of 16 positions (one wave's DMA);
-// level-fed rings history + one tile.  Returns the LDS bytes, 0 if the group does not qualify.
-constexpr int kDeepTile = 128;  // vw_deep.hip kDeepT
-
-template <typename T>
-static int deep_plan(const Tuning& tu, const std::vector<LevelDesc>& lv, int jlo, int jhi, int L, int64_t N,
-                     bool inverse, DeepArgs<T>* a) {
-  constexpr int V = vec_width<T>();
-  const int C = 64 / (int)sizeof(T);
-  const int g = jhi - jlo + 1;
-  if (!(inverse ? tu.deep_inv : tu.deep) || g < 1 || g > kMaxGroup || !has_unrolled_taps(L)) return 0;
-  const int P = lv[jlo - 1].s;
-  if (P < C || P % C != 0 || N % P != 0 || N / P < 2 * kDeepTile) return 0;
-  for (int j = jlo; j <= jhi; ++j)
-    if (lv[j - 1].mode != kHaloPeriodic) return 0;
-  (void)V;
-  int caps[2 * kMaxGroup] = {}, nr = 0;
-  int64_t reach = 0;
-  const int D = inverse ? tu.deep_pf_inv : tu.deep_pf_fwd;
-  for (int k = 0; k < g; ++k) {
-    const int64_t H = (int64_t)(L - 1) << k;
-    reach += H;
-    const bool dma_fed = inverse ? (k == g - 1) : (k == 0);
-    caps[k] = dma_fed ? (int)round_up(H + (D + 1) * kDeepTile, 16) : (int)(H + kDeepTile);
-    if (inverse) caps[g + k] = (int)round_up(H + (D + 1) * kDeepTile, 16);
-  }
-  nr = inverse ? 2 * g : g;
-  int64_t pos = 0;
-  for (int r = 0; r < nr; ++r) pos += caps[r];
-  const int64_t bytes = pos * 64;
-  if (bytes > (int64_t)tu.deep_lds * 1024 || bytes > kLdsBytes) return 0;
-  if (a) {
-    a->P = P; a->C = C; a->nq = (int)(N / P); a->nb = P / C; a->g = g; a->N = (int)N;
-    a->warm = (int)round_up(reach, kDeepTile);
-    a->depth = D;
-    int64_t o = 0;
-    for (int r = 0; r < nr; ++r) { a->cap[r] = caps[r]; a->off[r] = (int)(o * C); o += caps[r]; }
-  }
-  return (int)bytes;
-}
-
-// Segments per residue block: enough workgroups for `deep_waves` per CU, each segment at least four
-// warm-ups long (the warm-up is recomputed per segment).
-template <typename T>
-static void deep_segments(const Tuning& tu, int cus, int64_t B, DeepArgs<T>* a) {
-  const int64_t wg0 = B * a->nb;
-  int64_t seg = std::max<int64_t>(1, ((int64_t)tu.deep_waves * cus + wg0 - 1) / wg0);
-  seg = std::min<int64_t>(seg, std::max<int64_t>(1, a->nq / (4 * (int64_t)a->warm)));
-  a->seg = (int)seg;
-  a->seglen = (int)round_up((a->nq + seg - 1) / seg, kDeepTile);
-  a->seg = (int)((a->nq + a->seglen - 1) / a->seglen);
-}
-
 // ------------------------------------------------------------------------------------------------
 // VW_FLAG_REF_NONFINITE (vw_ref.hip): after the fast kernels, flag the rows holding a non-finite value
 // in any of `planes` (the call's inputs and outputs: an overflow to Inf inside the cascade shows in an
 // output), then recompute those rows with the reference's full-tap loops.  Stream-ordered, capturable
-// once the workspace has grown.
+// once the workspace has grown.  Row flags and scratch (`grid` workgroups) are the plan's reservation,
+// made before the launches.
 template <typename T>
 struct ScanPlane {
   const T* p;
@@ -1178,14 +795,9 @@ struct ScanPlane {
 
 template <typename T>
 static vw_status ref_nonfinite(vw_ctx* c, const std::vector<ScanPlane<T>>& planes, RefArgs<T>& r,
-                               bool inverse, bool flagged) {
+                               bool inverse, bool flagged, int grid) {
   const int64_t B = r.B, N = r.N;
   if ((int)planes.size() > kRefPlanes) return fail(VW_ERR_ARG, "too many planes for the non-finite scan");
-  // rows recomputed at once: one workgroup each, two running-approximation rows of scratch (<= 512 MiB)
-  int64_t grid = std::min<int64_t>(B, c->tune.ref_grid > 0 ? c->tune.ref_grid : 2LL * c->cus);
-  grid = std::max<int64_t>(1, std::min<int64_t>(grid, ((int64_t)512 << 20) / (2 * N * (int64_t)sizeof(T))));
-  VW_TRY(ensure_nf(c, B));
-  VW_TRY(ensure_ws(c, (size_t)grid * 2 * (size_t)N * sizeof(T)));
   // timing families: "ref_nonfinite" (the cascade over rows the fast kernel flagged), "ref_nonfinite_scan"
   // (scan + cascade)
   LaunchTimer lt(c, flagged ? "ref_nonfinite" : "ref_nonfinite_scan");
@@ -1216,679 +828,229 @@ static hipError_t mfma_forward(const FwdArgs<double>&, int, hipStream_t) { retur
 static hipError_t mfma_inverse(const InvArgs<float>& a, int lds, hipStream_t st) { return launch_inverse_mfma(a, lds, st); }
 static hipError_t mfma_inverse(const InvArgs<double>&, int, hipStream_t) { return hipErrorNotSupported; }
 
-static int ref_mode(int boundary) {
-  return boundary == VW_PERIODIC ? kHaloPeriodic : boundary == VW_ZERO_PADDING ? kHaloZero : kHaloSymmetric;
-}
-
 // ------------------------------------------------------------------------------------------------
-// Forward (multi-level and single-level share this path).
-template <typename T>
-static vw_status forward_impl(vw_ctx* c, const T* x, int64_t B, int64_t N, int64_t ldx, const double* lo,
-                              const double* hi, int L, int boundary, int J, unsigned flags, T* details, T* approx,
-                              bool single_level, int mode_override, T* const* hist, bool hist_update,
-                              T* const* hist_snap = nullptr, bool hist_first = false) {
-  constexpr int V = vec_width<T>();
-  VW_TRY(capture_guard(c, flags));
-  const bool fma = flags & VW_FLAG_FMA;
-  const bool validate = flags & VW_FLAG_VALIDATE;
-  const int64_t nvec = (N + V - 1) / V;
+// Executors.  Selection is vw_plan.cpp's: plan_forward / plan_inverse return which kernels run with what
+// launch shape and layout, which buffers they read and write, and what must be reserved.  The code below
+// adds the pointers and issues the launches; it decides nothing.
 
-  std::vector<LevelDesc> lv(J);
-  int max_hl = 0;
-  const int npow2 = next_pow2(N);
-  for (int j = 1; j <= J; ++j) {
-    LevelDesc& d = lv[j - 1];
-    memset(&d, 0, sizeof(d));
-    d.s = 1 << (j - 1);
-    const int64_t Lj = vw_upsampled_length(L, j);
-    d.hl = (int)(Lj - 1);
-    d.hr = 0;
-    d.hist_len = (int)(Lj - 1);
-    if (boundary == VW_PERIODIC) {
-      d.mode = kHaloPeriodic;
-      // MultiLevelMODWTTransform.applyScaledMODWT :734-742 + FftHeuristics :30-34
-      if ((flags & VW_FLAG_FFT_SWITCH) && !single_level && !(N < 64 || Lj > N / 2) && N >= 1024 &&
-          (double)Lj > N * (1.0 / 8.0) && !is_pow2(N))
-        d.mode = kHaloFftPad;
-    } else {
-      d.mode = boundary == VW_ZERO_PADDING ? kHaloZero : kHaloSymmetric;
-    }
-    if (mode_override >= 0) d.mode = mode_override;
-    max_hl = std::max(max_hl, d.hl);
-  }
-  // VW_FLAG_REF_NONFINITE on a streaming block: keep the histories this block reads (the kernels
-  // overwrite them) for the rows vw_ref.hip recomputes
-  if ((flags & VW_FLAG_REF_NONFINITE) && hist && hist_update && hist_snap && !hist_first && J >= 2)
-    for (int j = 0; j < J; ++j)
-      if (lv[j].hist_len > 0)
-        VW_HIP(hipMemcpyAsync(hist_snap[j], hist[j], (size_t)B * lv[j].hist_len * sizeof(T), hipMemcpyDeviceToDevice,
-                              c->stream));
-
-  const int hlpad = (int)round_up(max_hl, V);
-  int threads = 0, lds = 0, nv = 4;
-  // Level buffers: two (one barrier per level) or one (two barriers per level, but half the LDS:
-  // twice the workgroups per CU).  Measured on MI355X (db4 J=6, 4096 x 4096 fp64): two buffers win
-  // whenever the persistent forward (which needs them) runs -- FMA and EXACT alike; without it the
-  // EXACT kernel is faster with one buffer (more workgroups to overlap its longer arithmetic).
-  // VW_FWD_BUF=1|2 overrides.
-  //
-  // Persistent variant (vw_device.h k_forward_persist): next row by LDS-DMA during the last level.
-  // Its contract: two buffers, full slabs of whole waves, rows in 64-vector chunks, no validation
-  // or streaming history.  VW_FWD_PERSIST=0 disables it.
-  const Tuning& tu = c->tune;
-  const bool persist_on = tu.fwd_persist;
-  // the unvalidated callers' NaN spread through the zero taps (single level and J = 1 have none); a
-  // streaming block that updates its history needs the snapshot of the histories it read (stream_run)
-  const bool ref_nf = (flags & VW_FLAG_REF_NONFINITE) && !validate && !single_level && J >= 2 &&
-                      !(flags & VW_FLAG_FFT_SWITCH) && (!hist || !hist_update || hist_first || hist_snap);
-  bool nf_probed = false;
-  const bool io_aligned = (ldx % V == 0) && (N % V == 0) && aligned16(x) && aligned16(details) && aligned16(approx);
-  auto persist_ok = [&](int th, int nvv, bool ft) {
-    return persist_on && io_aligned && ft && nvv == 4 && !validate && !hist && (int64_t)th * nvv == nvec &&
-           th % 64 == 0 && nvec % 64 == 0 && has_unrolled_taps(L) && J >= 1;
-  };
-  const int64_t region = round_up(hlpad + nvec * V + V, V);
-  bool dbl = tu.fwd_buf ? tu.fwd_buf == 2 : true;
-  bool fused = false, fit = false;
-  // NV = 2 (1024-thread workgroups) only where the unrolled kernel will run (it has no runtime-L form)
-  const int fwd_nv2 = (tu.fwd_nv == 2 && io_aligned && L <= 8 && L <= tu.unroll_max && has_unrolled_taps(L) &&
-                       !(tu.blk > 0 && L >= tu.blk)) ? 2 : 0;
-  if (J <= kMaxLevels && !tu.force_tiled) {
-    if (dbl) dbl = fused_plan(tu, N, V, sizeof(T), 2 * region, &threads, &nv, &lds, &fit, fwd_nv2);
-    if (dbl && !tu.fwd_buf && !fma && !persist_ok(threads, nv, fit)) dbl = false;  // EXACT without persistence
-    fused = dbl || fused_plan(tu, N, V, sizeof(T), region, &threads, &nv, &lds, &fit, fwd_nv2);
-  }
-  if (fused && nv == 2 && !(fit && (int64_t)threads * 2 == nvec)) return fail(VW_ERR_STATE, "NV=2 plan without full slabs");
-  if (fused) {
-    for (int j = 0; j < J; ++j) set_halo_images(lv[j], N, npow2, V, threads, nv);
-    FwdArgs<T> a;
-    memset(&a, 0, sizeof(a));
-    a.x = x; a.ldx = ldx; a.details = details; a.approx = approx; a.B = B; a.N = (int)N; a.J = J;
-    a.npow2 = npow2; a.hlpad = hlpad; a.region1 = dbl ? (int)region : 0;
-    a.vec_io = (ldx % V == 0) && (N % V == 0) && aligned16(x) && aligned16(details) && aligned16(approx);
-    a.unrolled = a.vec_io && fit && L <= tu.unroll_max;
-    a.validate = validate; a.bad = c->bad;
-    a.rev = tu.fwd_rev;
-    a.level_ct = tu.level_ct;
-    // non-temporal LDS-DMA of the rows: faster at <= 2 signals per CU (512 rows: forward 0.0268 -> 0.0245 ms),
-    // slower on full batches (4096 rows: 0.218-0.225 -> 0.234-0.243 ms; profiles/r04/ab_rotate_default_*.log,
-    // ab_overlap_direct_512.log)
-    a.dma_nt = tu.dma_nt >= 0 ? tu.dma_nt : (B <= 2LL * c->cus ? 1 : 0);
-    for (int j = 0; j < J; ++j) a.hist[j] = hist ? hist[j] : nullptr;
-    a.hist_update = hist_update ? 1 : 0;
-    a.taps = L;
-    copy_taps(a.lo, lo, L);
-    copy_taps(a.hi, hi, L);
-    for (int j = 0; j < J; ++j) a.lv[j] = lv[j];
-    if (validate) VW_HIP(hipMemsetAsync(c->bad, 0xFF, sizeof(unsigned long long), c->stream));
-    const bool persist = dbl && a.unrolled && persist_ok(threads, nv, fit);
-    // register-blocked PERIODIC forward for long filters (vw_device.h k_forward_blk): padded layouts
-    int blk_lds = 0;
-    // (NV = 8, 1024-thread workgroups: with its taps from the kernel arguments (round 4, 99 VGPRs, no
-    // spills) the blocked forward beats the fused one at sym8 N = 16384: 5.27-5.29 -> 4.76 ms,
-    // profiles/r04/ab_blk_fwd8_ktaps_sym8.log; VW_BLK_FWD8=0 restores the fused kernel)
-    // (listed tap counts only: launch_forward_blk has no runtime-L form)
-    if (tu.blk > 0 && L >= tu.blk && has_unrolled_taps(L) && a.unrolled && !validate && !hist &&
-        (int64_t)threads * nv == nvec && (nv == 4 || (nv == 8 && tu.blk_fwd8))) {
-      bool okb = true;
-      int hlv = 0;
-      for (int j = 0; j < J; ++j) {
-        if (lv[j].mode != kHaloPeriodic) okb = false;
-        hlv = std::max<int>(hlv, (int)(((int64_t)(L - 1) * lv[j].s + V - 1) / V));
-      }
-      // the kernel reads at wave-uniform (NV = 8) or compile-time (NV = 4) offsets when the halo is whole
-      // pad groups (16 vectors)
-      if (round_up(hlv, 16) <= nvec) hlv = (int)round_up(hlv, 16);
-      const int mJ = std::max(1, lv[J - 1].s / V);
-      if (nvec % ((int64_t)nv * mJ) != 0 || hlv > nvec) okb = false;
-      auto buf_of = [&](int tight) {
-        int64_t bf = 0;
-        for (int j = 0; j < J; ++j) {
-          int sh, pd;
-          blk_layout_host(lv[j].s / V, nv, &sh, &pd, tight);
-          const int64_t u = hlv + nvec - 1;
-          bf = std::max(bf, u + (u >> sh) * pd + 1);
-        }
-        return bf;
-      };
-      int64_t buf = buf_of(0);
-      if (buf * 16 + 2 * L * (int64_t)sizeof(T) > kLdsBytes && nv >= 8) {
-        a.blk_tight = 1;
-        buf = buf_of(1);
-      }
-      if (okb && buf * 16 <= kLdsBytes) {
-        const bool two = 2 * buf * 16 <= 80 * 1024;  // two buffers only where two workgroups still fit a CU
-        a.region1 = two ? (int)(buf * V) : 0;
-        a.hlpad = hlv * V;
-        a.tap_lds = (int)(buf * V * (two ? 2 : 1));
-        blk_lds = (int)(buf * 16 * (two ? 2 : 1)) + 2 * L * (int)sizeof(T);
-        if (blk_lds > kLdsBytes) blk_lds = 0;
-      }
-    }
-    // fp32 FMA, PERIODIC, long filters: the matrix-core forward (vw_mfma.hip, VW_MFMA bit 0)
-    int mfma_lds = 0;
-    if constexpr (std::is_same<T, float>::value) {
-      bool ok = (tu.mfma & 1) && fma && !single_level && a.vec_io && !validate && !hist && mfma_supported(L, N);
-      for (int j = 0; ok && j < J; ++j) ok = lv[j].mode == kHaloPeriodic;
-      const int H = ok ? mfma_halo(L, J) : 0;
-      const int region = ok ? mfma_region((int)N + H) : 0;  // padded LDS layout (vw_mfma.hip ph)
-      const int scratch = 8 * 256 + 4;  // the forward's per-wave transpose scratch (<= 8 waves), aligned
-      if (ok && H <= N && (int64_t)(region + 2 * L + scratch) * 4 <= kLdsBytes) {
-        a.hlpad = H;
-        a.tap_lds = region;
-        mfma_lds = (int)((region + 2 * L + scratch) * 4);
-      }
-    }
-    // VW_FLAG_REF_NONFINITE: the persistent and the register-blocked forward probe their a_J (no scan pass
-    // afterwards)
-    if (ref_nf && !mfma_lds && (blk_lds || persist)) {
-      VW_TRY(ensure_nf(c, B));
-      a.nf_flag = c->nf;
-      nf_probed = true;
-    }
-    {
-      LaunchTimer lt(c, "forward");
-      hipError_t e = mfma_lds ? mfma_forward(a, mfma_lds, c->stream)
-                   : blk_lds ? launch_forward_blk<T>(a, threads, blk_lds, fma, nv, c->stream)
-                   : persist ? launch_forward_persist<T>(a, threads, lds, fma, nv, c->stream)
-                             : launch_forward_fused<T>(a, threads, lds, fma, nv, c->stream);
-      if (e != hipSuccess) return fail(VW_ERR_DEVICE, "forward launch failed: %s", hipGetErrorString(e));
-    }
-  } else {
-    // Per-level path for long signals: ping-pong the running approximation through the workspace.
-    // Deep levels (s >= kSweepMinS) run as column sweeps, shallow ones as LDS tiles with a halo.
-    for (int j = 1; hist && j <= J; ++j)
-      if (lv[j - 1].hist_len > N) return fail(VW_ERR_UNSUPPORTED, "streaming block shorter than level %d history", j);
-    const int tile_max = tu.fwd_tile ? tu.fwd_tile / V * V : 256 * kNV * V;
-    const size_t plane = (size_t)B * (size_t)N;
-    const vw_status st = ensure_ws(c, 2 * plane * sizeof(T) + 256);
-    if (st != VW_OK) return st;
-    T* tmp[2] = {reinterpret_cast<T*>(c->ws), reinterpret_cast<T*>(c->ws) + plane};
-    if (validate) VW_HIP(hipMemsetAsync(c->bad, 0xFF, sizeof(unsigned long long), c->stream));
-    const T* src = x;
-    int64_t lda = ldx;
-    const int mtile = multi_tile<T>(tu);
-    const std::vector<int> groups = level_groups(tu, lv, J, L, V, mtile, !validate && !hist);
-    for (int j = 1; j <= J; ++j) {
-      T* const nxt = (src == tmp[0]) ? tmp[1] : tmp[0];  // never the level's own input
-      // streaming deep group from level j: the longest run j..je within the LDS budget
-      if (groups[j - 1] == 1 && !validate && !hist && (lda % V) == 0 && aligned16(src) && aligned16(details) &&
-          aligned16(approx) && deep_plan<T>(tu, lv, j, j, L, N, false, nullptr)) {
-        int je = j;
-        while (je < J && groups[je] == 1 && deep_plan<T>(tu, lv, j, je + 1, L, N, false, nullptr)) ++je;
-        DeepArgs<T> d;
-        memset(&d, 0, sizeof(d));
-        const int lds = deep_plan<T>(tu, lv, j, je, L, N, false, &d);
-        deep_segments<T>(tu, c->cus, B, &d);
-        d.src = src; d.lda = lda; d.B = B; d.taps = L;
-        d.out = (je == J) ? approx : nxt;
-        if (ref_nf && je == J) {  // the deep launch writes a_J: it probes it (VW_FLAG_REF_NONFINITE)
-          VW_TRY(ensure_nf(c, B));
-          d.nf_flag = c->nf;
-          nf_probed = true;
-        }
-        for (int k = 0; k < d.g; ++k) d.out_d[k] = details + (size_t)(j - 1 + k) * plane;
-        copy_taps(d.lo, lo, L);
-        copy_taps(d.hi, hi, L);
-        {
-          LaunchTimer lt(c, "forward_level");
-          hipError_t e = launch_deep<T>(d, lds, fma, false, c->stream);
-          if (e != hipSuccess) return fail(VW_ERR_DEVICE, "forward deep launch failed: %s", hipGetErrorString(e));
-        }
-        src = d.out;
-        lda = N;
-        j = je;
-        continue;
-      }
-      if (groups[j - 1] >= 2) {
-        const int g = groups[j - 1], je = j + g - 1;
-        MultiArgs<T> m;
-        memset(&m, 0, sizeof(m));
-        m.src_a = src; m.lda = lda;
-        m.out_a = (je == J) ? approx : nxt;
-        bool al = aligned16(src) && aligned16(m.out_a);
-        for (int k = 0; k < g; ++k) {
-          m.out_d[k] = details + (size_t)(j - 1 + k) * plane;
-          al = al && aligned16(m.out_d[k]);
-        }
-        m.ext[g] = 0;
-        for (int k = g - 1; k >= 0; --k)
-          m.ext[k] = m.ext[k + 1] + (int)round_up((int64_t)(L - 1) * lv[j - 1 + k].s, V);
-        m.B = B; m.N = (int)N; m.tile = mtile; m.nlev = g; m.s0 = lv[j - 1].s;
-        m.region = (int)round_up(m.ext[0] + mtile + V, V);
-        m.vec_io = (N % V == 0) && (lda % V == 0) && al;
-        m.taps = L;
-        copy_taps(m.lo, lo, L);
-        copy_taps(m.hi, hi, L);
-        {
-          LaunchTimer lt(c, "forward_level");
-          hipError_t e = launch_forward_multi<T>(m, (int)(2 * m.region * sizeof(T)), fma, c->stream);
-          if (e != hipSuccess) return fail(VW_ERR_DEVICE, "forward multi-level launch failed: %s", hipGetErrorString(e));
-        }
-        src = m.out_a;
-        lda = N;
-        j = je;
-        continue;
-      }
-      LevelArgs<T> a;
-      memset(&a, 0, sizeof(a));
-      a.lv = lv[j - 1];
-      const int hp = (int)round_up(a.lv.hl, V);
-      // deep levels have long halos: shrink the tile so tile + halo fits LDS
-      const int64_t fit = ((int64_t)kLdsBytes / (int64_t)sizeof(T) - hp - 2 * V) / V * V;
-      const int tile = (int)std::min<int64_t>(tile_max, fit);
-      if (tile < 64 * V) return fail(VW_ERR_UNSUPPORTED, "level %d halo (%d samples) exceeds LDS", j, a.lv.hl);
-      const int64_t elems = hp + tile + V;
-      a.src_a = src; a.lda = lda;
-      a.out_a = (j == J) ? approx : nxt;
-      a.out_d = details + (size_t)(j - 1) * plane;
-      a.hist = hist ? hist[j - 1] : nullptr;
-      a.B = B; a.N = (int)N; a.tile = tile; a.hlpad = hp;
-      a.vec_io = (N % V == 0) && (lda % V == 0) && aligned16(src) && aligned16(a.out_a) && aligned16(a.out_d);
-      a.validate = validate; a.bad = c->bad; a.npow2 = npow2; a.taps = L;
-      copy_taps(a.lo, lo, L);
-      copy_taps(a.hi, hi, L);
-      const bool sweep = a.lv.s >= kSweepMinS && has_unrolled_taps(L) && !tu.no_sweep;
-      {
-        LaunchTimer lt(c, "forward_level");
-        hipError_t e;
-        if (sweep) {
-          a.tile = tu.sweep_qc;
-          e = launch_forward_sweep<T>(a, fma, c->stream);
-        } else {
-          e = launch_forward_level<T>(a, (int)(elems * sizeof(T)), fma, c->stream);
-        }
-        if (e != hipSuccess) return fail(VW_ERR_DEVICE, "forward level launch failed: %s", hipGetErrorString(e));
-      }
-      // streaming: this level's new left history = the last L_j - 1 samples of its input
-      // (BatchStreamingMODWT.updateHistoryFromSoA :337-352); read by this level's kernel first
-      if (hist && hist_update) {
-        hipError_t e = launch_history_update<T>(src, lda, hist[j - 1], hist[j - 1], B, (int)N, a.lv.hist_len,
-                                                c->stream);
-        if (e != hipSuccess) return fail(VW_ERR_DEVICE, "history update failed: %s", hipGetErrorString(e));
-      }
-      src = a.out_a;
-      lda = N;
-    }
-  }
-  if (ref_nf) {
-    // a_J alone: every non-finite level input (x, a_1 .. a_{J-1}, a history) reaches it (vw_ref.hip)
-    std::vector<ScanPlane<T>> planes{{approx, N, 0}};
-    RefArgs<T> r;
-    memset(&r, 0, sizeof(r));
-    r.x = x; r.ldx = ldx; r.details = details; r.approx = approx;
-    r.B = B; r.N = (int)N; r.J = J; r.L = L; r.mode = ref_mode(boundary);
-    if (hist) {  // BatchStreamingMODWT block / flush: the histories the block read, and the ones it leaves
-      r.hist_mode = 1;
-      r.hist_first = hist_first ? 1 : 0;
-      for (int j = 0; j < J; ++j) {
-        const int hl = lv[j].hist_len;
-        r.hist_len[j] = hl;
-        r.hist_old[j] = hist_first ? nullptr : (hist_update ? hist_snap[j] : hist[j]);
-        r.hist_new[j] = hist_update ? hist[j] : nullptr;
-      }
-    }
-    copy_taps(r.lo, lo, L);
-    copy_taps(r.hi, hi, L);
-    VW_TRY(ref_nonfinite<T>(c, planes, r, false, nf_probed));
-  }
-  if (validate) {
-    unsigned long long bad = 0;
-    vw_status st = read_bad(c, &bad);
-    if (st != VW_OK) return st;
-    st = report_bad(bad, N);
-    if (st != VW_OK) return st;
-  }
-  if (flags & VW_FLAG_SYNC) VW_HIP(hipStreamSynchronize(c->stream));
+// Everything a plan lists, before the first launch: a failure leaves nothing queued (no row flags set by a
+// probing kernel whose fix-up then cannot run).
+static vw_status reserve(vw_ctx* c, const PlanReserve& r) {
+  if (r.ws_bytes) VW_TRY(ensure_ws(c, r.ws_bytes));
+  if (r.nf_rows) VW_TRY(ensure_nf(c, r.nf_rows));
   return VW_OK;
 }
 
-// ------------------------------------------------------------------------------------------------
-// Inverse
-template <typename T>
-static vw_status inverse_impl(vw_ctx* c, const T* details, const T* approx, int64_t B, int64_t N, const double* lo,
-                              const double* hi, int L, int wid, int boundary, int J, unsigned detail_mask,
-                              int approx_zero, unsigned flags, T* y, bool single_level, const T* thr, int soft,
-                              int64_t thr_ld = 0) {
-  constexpr int V = vec_width<T>();
-  VW_TRY(capture_guard(c, flags));
-  const bool fma = flags & VW_FLAG_FMA;
-  const int64_t nvec = (N + V - 1) / V;
-  const int tmax = (int)(nvec * V - 1);
-  const bool pair = single_level || boundary == VW_ZERO_PADDING;
-  // the unvalidated callers' NaN spread through the zero taps (single level and J = 1 have none)
-  const bool ref_nf = (flags & VW_FLAG_REF_NONFINITE) && !single_level && J >= 2;
-  bool nf_probed = false;
+static const char* const kStepNames[] = {"deep", "multi-level", "level-group", "level", "level"};
+static vw_status step_failed(const char* dir, int kind, hipError_t e) {
+  return fail(VW_ERR_DEVICE, "%s %s launch failed: %s", dir, kStepNames[kind - kStepDeep], hipGetErrorString(e));
+}
 
-  std::vector<LevelDesc> lv(J);
-  int max_hl = 0, max_hr = 0;
-  for (int j = 1; j <= J; ++j) {
-    LevelDesc& d = lv[j - 1];
-    memset(&d, 0, sizeof(d));
-    d.s = 1 << (j - 1);
-    d.use_d = (detail_mask >> (j - 1)) & 1u;
-    d.mode = boundary == VW_PERIODIC ? kHaloPeriodic : boundary == VW_ZERO_PADDING ? kHaloZero : kHaloSymmetric;
-    if (boundary == VW_SYMMETRIC && !single_level) {
-      int ap, dh, dp, dg;
-      sym_decide(wid, L, j, &ap, &dh, &dp, &dg);
-      const int tauH = compute_tau(L, j) + dh;
-      const int tauG = compute_tau(L, j) + dg;
-      d.dir_a = ap ? 1 : -1; d.off_a = ap ? -tauH : tauH;
-      d.dir_d = dp ? 1 : -1; d.off_d = dp ? -tauG : tauG;
-    } else if (boundary == VW_SYMMETRIC) {
-      const int dir = (flags & VW_FLAG_BATCH_SYM_INVERSE) ? 1 : -1;  // inverseBatchOptimized (t+l) vs inverse (t-l)
-      d.dir_a = d.dir_d = dir; d.off_a = d.off_d = 0;
+// Per-level forward: the plan's steps, ping-ponging the running approximation through the workspace.
+template <typename T>
+static vw_status forward_steps(vw_ctx* c, const FwdCall<T>& k, const FwdPlan<T>& p) {
+  const size_t plane = (size_t)k.B * (size_t)k.N;
+  T* const ws[2] = {reinterpret_cast<T*>(c->ws), reinterpret_cast<T*>(c->ws) + plane};
+  for (const PlanStep<T>& s : p.steps) {
+    const T* const src = s.src == kBufIn ? k.x : ws[s.src - kBufWs0];
+    T* const dst = s.dst == kBufOut ? k.approx : ws[s.dst - kBufWs0];
+    T* const det = k.details + (size_t)(s.jlo - 1) * plane;  // d of the step's first level
+    hipError_t e;
+    if (s.kind == kStepDeep) {
+      DeepArgs<T> d = s.deep;
+      d.src = src; d.out = dst;
+      d.nf_flag = s.probe ? c->nf : nullptr;
+      for (int g = 0; g < d.g; ++g) d.out_d[g] = det + (size_t)g * plane;
+      copy_taps(d.lo, k.lo, k.L);
+      copy_taps(d.hi, k.hi, k.L);
+      LaunchTimer lt(c, "forward_level");
+      e = launch_deep<T>(d, s.lds, p.fma, false, c->stream);
+    } else if (s.kind == kStepMulti) {
+      MultiArgs<T> m = s.multi;
+      m.src_a = src; m.out_a = dst;
+      for (int g = 0; g < m.nlev; ++g) m.out_d[g] = det + (size_t)g * plane;
+      copy_taps(m.lo, k.lo, k.L);
+      copy_taps(m.hi, k.hi, k.L);
+      LaunchTimer lt(c, "forward_level");
+      e = launch_forward_multi<T>(m, s.lds, p.fma, c->stream);
     } else {
-      d.dir_a = d.dir_d = 1; d.off_a = d.off_d = 0;
+      LevelArgs<T> a = s.lvl;
+      a.src_a = src; a.out_a = dst; a.out_d = det;
+      a.hist = k.hist ? k.hist[s.jlo - 1] : nullptr;
+      a.bad = c->bad;
+      copy_taps(a.lo, k.lo, k.L);
+      copy_taps(a.hi, k.hi, k.L);
+      LaunchTimer lt(c, "forward_level");
+      e = s.kind == kStepSweep ? launch_forward_sweep<T>(a, p.fma, c->stream)
+                               : launch_forward_level<T>(a, s.lds, p.fma, c->stream);
     }
-    int hl = 0, hr = 0;
-    branch_extent((int)N, tmax, L, d.s, d.dir_a, d.off_a, &hl, &hr);
-    branch_extent((int)N, tmax, L, d.s, d.dir_d, d.off_d, &hl, &hr);
-    d.hl = hl; d.hr = hr;
-    max_hl = std::max(max_hl, hl);
-    max_hr = std::max(max_hr, hr);
-  }
-  const int hlpad = (int)round_up(max_hl, V);
-  const int64_t region = round_up(hlpad + nvec * V + max_hr + V, V);
-  int threads = 0, lds = 0, nv = 4;
-  // Pairwise sums need a_j and d_j together (two regions).  Sequential sums time-share one region
-  // (k_inverse_seq, four barriers per level) -- measured faster on MI355X than two buffers
-  // (k_inverse_db, two barriers per level) because twice the workgroups fit per CU; VW_INV_BUF=2
-  // selects the latter.
-  const Tuning& tu = c->tune;
-  // Two LDS buffers (two barriers per level, two workgroups per CU) vs one (four barriers, three per
-  // CU): with at most 2 signals per CU the occupancy of the one-buffer kernel is not reached and the
-  // shorter per-level chain wins (measured on MI355X, db4 x 4096, inverse ms one / two buffers:
-  // B = 512 0.0335 / 0.0324, B = 768 0.0462 / 0.0504, B = 1024 0.0594 / 0.0606 --
-  // profiles/r02/ab_small_batch.log, ab_inv_buf_1024_768.log); VW_INV_BUF=1|2 overrides.
-  // Long PERIODIC filters (L >= VW_BLK) keep the register-blocked single-buffer kernel (k_inverse_blk
-  // needs !db) at small batches too: its NV+L-1 LDS reads per branch outweigh the shorter barrier chain.
-  // Only listed tap counts have a k_inverse_blk: other lengths follow the short filters' policy.
-  const bool blk_pref = tu.blk > 0 && L >= tu.blk && has_unrolled_taps(L) && boundary == VW_PERIODIC;
-  bool db = !pair && (tu.inv_buf ? tu.inv_buf == 2 : (B <= 2LL * c->cus && !blk_pref));
-  bool fused = false, fit = false;
-  const bool inv_io = (N % V == 0) && aligned16(details) && aligned16(approx) && aligned16(y);
-  const int inv_nv2 = (tu.inv_nv == 2 && inv_io && L <= 8 && L <= tu.unroll_max && has_unrolled_taps(L)) ? 2 : 0;
-  if (!tu.force_tiled) {
-    if (pair || db) fused = fused_plan(tu, N, V, sizeof(T), 2 * region, &threads, &nv, &lds, &fit, inv_nv2);
-    if (!fused && !pair) {
-      db = false;
-      fused = fused_plan(tu, N, V, sizeof(T), region, &threads, &nv, &lds, &fit, inv_nv2);
+    if (e != hipSuccess) return step_failed("forward", s.kind, e);
+    if (s.hist_update) {
+      e = launch_history_update<T>(src, s.lvl.lda, k.hist[s.jlo - 1], k.hist[s.jlo - 1], k.B, (int)k.N,
+                                   s.lvl.lv.hist_len, c->stream);
+      if (e != hipSuccess) return fail(VW_ERR_DEVICE, "history update failed: %s", hipGetErrorString(e));
     }
   }
-  if (fused) {
-    for (int j = 0; j < J; ++j) set_halo_images(lv[j], N, 0, V, threads, nv);
-    InvArgs<T> a;
-    memset(&a, 0, sizeof(a));
-    a.details = details; a.approx = approx; a.y = y; a.B = B; a.N = (int)N; a.J = J;
-    a.db = db ? 1 : 0;
-    a.hlpad_a = hlpad; a.hlpad_d = hlpad; a.region_d = (int)region;
-    a.vec_io = (N % V == 0) && aligned16(details) && aligned16(approx) && aligned16(y);
-    a.unrolled = a.vec_io && fit && L <= tu.unroll_max;
-    a.pair = pair; a.approx_zero = approx_zero; a.thr = thr; a.thr_ld = thr_ld; a.soft = soft; a.taps = L;
-    a.rev = tu.inv_rev;
-    a.level_ct = tu.level_ct;
-    a.full = tu.level_ct && a.unrolled && (int64_t)threads * nv == nvec;
-    // register-blocked PERIODIC inverse for long filters (vw_device.h k_inverse_blk)
-    if (tu.blk > 0 && L >= tu.blk && has_unrolled_taps(L) && nv != 2 && !pair && !db && boundary == VW_PERIODIC &&
-        a.unrolled && (int64_t)threads * nv == nvec) {
-      bool okb = true;
-      int64_t buf = 0;
-      const int mJ = std::max(1, lv[J - 1].s / V);
-      if (nvec % ((int64_t)nv * mJ) != 0) okb = false;
-      int64_t buf_t = 0;
-      for (int j = 0; j < J && okb; ++j) {
-        if (lv[j].dir_a != 1 || lv[j].dir_d != 1 || lv[j].off_a != 0 || lv[j].off_d != 0) okb = false;
-        const int64_t hrv = ((int64_t)(L - 1) * lv[j].s + V - 1) / V;
-        if (hrv > nvec) okb = false;
-        int sh, pd;
-        const int64_t u = nvec + hrv - 1;
-        blk_layout_host(lv[j].s / V, nv, &sh, &pd);
-        buf = std::max(buf, u + (u >> sh) * pd + 1);
-        blk_layout_host(lv[j].s / V, nv, &sh, &pd, 1);
-        buf_t = std::max(buf_t, u + (u >> sh) * pd + 1);
-      }
-      const int64_t taps_b = 2 * L * (int64_t)sizeof(T);
-      if (okb && buf * 16 + taps_b > kLdsBytes && nv >= 8 && buf_t * 16 + taps_b <= kLdsBytes) {
-        a.blk_tight = 1;  // sparse padding so the level fits (sym8 at N = 16384)
-        buf = buf_t;
-      }
-      if (okb && buf * 16 + taps_b <= kLdsBytes) {
-        a.blk = 1;
-        a.tap_lds = (int)(buf * V);
-        lds = (int)(buf * 16) + 2 * L * (int)sizeof(T);
-      }
-    }
-    copy_taps(a.lo, lo, L);
-    copy_taps(a.hi, hi, L);
-    for (int j = 0; j < J; ++j) a.lv[j] = lv[j];
-    // (A persistent form that loads the next signal's approximation during level 1 was measured
-    // slower on MI355X: 3 resident workgroups per CU do not divide the batch evenly, and the dynamic
-    // dispatch of one-signal workgroups balances better.)
-    // fp32 FMA, PERIODIC sequential sums, long filters: the matrix-core inverse (vw_mfma.hip, VW_MFMA bit 1)
-    int mfma_lds = 0;
-    if constexpr (std::is_same<T, float>::value) {
-      bool ok = (tu.mfma & 2) && fma && !pair && boundary == VW_PERIODIC && a.vec_io && mfma_supported(L, N);
-      for (int j = 0; ok && j < J; ++j) ok = lv[j].dir_a == 1 && lv[j].dir_d == 1 && lv[j].off_a == 0 && lv[j].off_d == 0;
-      const int H = ok ? mfma_halo(L, J) : 0;
-      const int region = ok ? mfma_region((int)N + H) : 0;
-      if (ok && H <= N && (int64_t)(region + 2 * L) * 4 <= kLdsBytes) {
-        a.hlpad_a = H;
-        a.tap_lds = region;
-        mfma_lds = (int)((region + 2 * L) * 4);
-      }
-    }
-    // VW_FLAG_REF_NONFINITE: the one-buffer sequential kernels (k_inverse_seq / k_inverse_blk, vw_inv.hip's
-    // choice) probe their output themselves (no scan pass afterwards)
-    if (ref_nf && !mfma_lds && !a.pair && !a.db) {
-      VW_TRY(ensure_nf(c, B));
-      a.nf_flag = c->nf;
-      nf_probed = true;
-    }
-    LaunchTimer lt(c, "inverse");
-    hipError_t e = mfma_lds ? mfma_inverse(a, mfma_lds, c->stream) : launch_inverse_fused<T>(a, threads, lds, fma, nv, c->stream);
-    if (e != hipSuccess) return fail(VW_ERR_DEVICE, "inverse launch failed: %s", hipGetErrorString(e));
+  return VW_OK;
+}
+
+// Forward (multi-level and single-level share this path).
+template <typename T>
+static vw_status forward_impl(vw_ctx* c, FwdCall<T> k) {
+  VW_TRY(capture_guard(c, k.flags));
+  k.cus = c->cus;
+  FwdPlan<T> p;
+  plan_forward(c->tune, k, &p);
+  if (p.error != VW_OK) return fail((vw_status)p.error, "%s", p.msg);
+  VW_TRY(reserve(c, p.res));
+  const LevelDesc* const lv = p.args.lv;
+  if (p.snapshot)
+    for (int j = 0; j < k.J; ++j)
+      if (lv[j].hist_len > 0)
+        VW_HIP(hipMemcpyAsync(k.hist_snap[j], k.hist[j], (size_t)k.B * lv[j].hist_len * sizeof(T),
+                              hipMemcpyDeviceToDevice, c->stream));
+  if (p.validate) VW_HIP(hipMemsetAsync(c->bad, 0xFF, sizeof(unsigned long long), c->stream));
+  if (p.fused) {
+    FwdArgs<T> a = p.args;
+    a.x = k.x; a.details = k.details; a.approx = k.approx;
+    a.bad = c->bad;
+    a.nf_flag = p.nf_probed ? c->nf : nullptr;
+    for (int j = 0; j < k.J; ++j) a.hist[j] = k.hist ? k.hist[j] : nullptr;
+    copy_taps(a.lo, k.lo, k.L);
+    copy_taps(a.hi, k.hi, k.L);
+    LaunchTimer lt(c, "forward");
+    hipError_t e = p.kernel == kFwdMfma    ? mfma_forward(a, p.lds, c->stream)
+                 : p.kernel == kFwdBlk     ? launch_forward_blk<T>(a, p.threads, p.lds, p.fma, p.nv, c->stream)
+                 : p.kernel == kFwdPersist ? launch_forward_persist<T>(a, p.threads, p.lds, p.fma, p.nv, c->stream)
+                                           : launch_forward_fused<T>(a, p.threads, p.lds, p.fma, p.nv, c->stream);
+    if (e != hipSuccess) return fail(VW_ERR_DEVICE, "forward launch failed: %s", hipGetErrorString(e));
   } else {
-    // 1024-sample tiles: two LDS regions of ~9 KiB keep many workgroups per CU (measured best on
-    // MI355X for db8 2^20-sample blocks; VW_INV_TILE overrides)
-    const int tile_max = tu.inv_tile ? tu.inv_tile / V * V : 1024;
-    const size_t plane = (size_t)B * (size_t)N;
-    const vw_status st = ensure_ws(c, 2 * plane * sizeof(T) + 256);
-    if (st != VW_OK) return st;
-    T* tmp[2] = {reinterpret_cast<T*>(c->ws), reinterpret_cast<T*>(c->ws) + plane};
-    const T* cur = approx_zero ? nullptr : approx;
-    // multi-level groups (PERIODIC sequential sums): start level of the group whose top is j
-    const int mtile = tu.multi_inv_tile >= 64 * V ? tu.multi_inv_tile / V * V : multi_tile<T>(tu);
-    const std::vector<int> groups = level_groups(tu, lv, J, L, V, mtile, !pair && boundary == VW_PERIODIC);
-    std::vector<int> start_of(J + 1, 0);
-    for (int j = 1; j <= J; ++j) {
-      if (groups[j - 1] < 2) continue;
-      int64_t ext = 0;  // k_inverse_multi holds (tile + reach) / V vectors in kMultiInvNI per thread
-      for (int k = 0; k < groups[j - 1]; ++k) ext += round_up((int64_t)(L - 1) * lv[j - 1 + k].s, V);
-      if ((mtile + ext) / V <= (int64_t)kMultiInvNI * 256) start_of[j + groups[j - 1] - 1] = j;
-    }
-    std::vector<char> in_group(J + 1, 0);  // levels inside a multi-level tile group
-    for (int e = 1; e <= J; ++e)
-      for (int k = start_of[e]; start_of[e] > 0 && k <= e; ++k) in_group[k] = 1;
-    for (int j = J; j >= 1; --j) {
-      T* const nxt = (cur == tmp[0]) ? tmp[1] : tmp[0];  // never the level's own input
-      // streaming deep group with top level j: the lowest jl whose group jl..j fits the LDS budget
-      if (!pair && boundary == VW_PERIODIC && !in_group[j] && aligned16(cur) && aligned16(details) &&
-          aligned16(y) && deep_plan<T>(tu, lv, j, j, L, N, true, nullptr)) {
-        int jl = j;
-        while (jl > 1 && !in_group[jl - 1] && deep_plan<T>(tu, lv, jl - 1, j, L, N, true, nullptr)) --jl;
-        DeepArgs<T> d;
-        memset(&d, 0, sizeof(d));
-        const int lds = deep_plan<T>(tu, lv, jl, j, L, N, true, &d);
-        deep_segments<T>(tu, c->cus, B, &d);
-        d.src = cur; d.lda = N; d.B = B; d.taps = L; d.soft = soft;
-        d.out = (jl == 1) ? y : nxt;
-        for (int k = 0; k < d.g; ++k) {
-          const LevelDesc& ld = lv[jl - 1 + k];
-          d.src_d[k] = ld.use_d ? details + (size_t)(jl - 1 + k) * plane : nullptr;
-          d.thr[k] = thr ? thr + (size_t)(jl - 1 + k) * (size_t)thr_ld : nullptr;
-        }
-        copy_taps(d.lo, lo, L);
-        copy_taps(d.hi, hi, L);
-        {
-          LaunchTimer lt(c, "inverse_level");
-          hipError_t e = launch_deep<T>(d, lds, fma, true, c->stream);
-          if (e != hipSuccess) return fail(VW_ERR_DEVICE, "inverse deep launch failed: %s", hipGetErrorString(e));
-        }
-        cur = d.out;
-        j = jl;
-        continue;
-      }
-      if (start_of[j] > 0) {
-        const int j0 = start_of[j], g = j - j0 + 1;
-        MultiArgs<T> m;
-        memset(&m, 0, sizeof(m));
-        m.src_a = cur;
-        m.out_a = (j0 == 1) ? y : nxt;
-        if (ref_nf && j0 == 1) {  // the group writes y: it probes it (VW_FLAG_REF_NONFINITE)
-          VW_TRY(ensure_nf(c, B));
-          m.nf_flag = c->nf;
-          nf_probed = true;
-        }
-        bool al = aligned16(cur) && aligned16(m.out_a);
-        for (int k = 0; k < g; ++k) {
-          const LevelDesc& d = lv[j0 - 1 + k];
-          m.src_d[k] = d.use_d ? details + (size_t)(j0 - 1 + k) * plane : nullptr;
-          m.thr[k] = thr ? thr + (size_t)(j0 - 1 + k) * (size_t)thr_ld : nullptr;
-          al = al && aligned16(m.src_d[k]);
-          m.ext[k] = (k > 0 ? m.ext[k - 1] : 0) + (int)round_up((int64_t)(L - 1) * d.s, V);
-        }
-        m.B = B; m.N = (int)N; m.tile = mtile; m.nlev = g; m.s0 = lv[j0 - 1].s;
-        m.region = (int)round_up(mtile + m.ext[g - 1] + V, V);
-        m.vec_io = (N % V == 0) && al;
-        m.soft = soft; m.taps = L;
-        m.rblk = tu.multi_rblk;
-        // register prefetch of d_{j-1} while level j computes: whole vectors, every tile of the group
-        m.pf = tu.multi_pf && m.vec_io && (int64_t)(mtile + m.ext[g - 1]) / V <= (int64_t)kMultiPF * 256;
-        // padded layout at the register-blocked levels (vw_device.h k_inverse_multi): needs the register
-        // paths (prefetch, blocked taps); the regions grow by one vector in eight
-        m.pad = tu.multi_pad && m.pf && m.rblk && has_unrolled_taps(L);
-        if (m.pad) {
-          const int nvmax = (mtile + m.ext[g - 1]) / V + 1;
-          m.region = (nvmax + nvmax / 8 + 1) * V;
-        }
-        // slack past D for the compile-time-stride reads (vw_device.h k_inverse_multi): 15*M <= 120 vectors
-        m.slack = 160;
-        m.ni = kMultiInvNI;
-        // four output vectors per thread (fp64, padded layouts): at NI = 8 a 2048-sample tile gives the
-        // register-blocked levels 129-144 threads of work, i.e. 2.0-2.3 of the workgroup's 4 waves (one SIMD idle,
-        // one mostly idle); at NI = 4 on the largest tile whose levels fit 256 threads (1792 for db8) all four
-        // waves work.  The group itself stays as planned above.
-        if (tu.multi_ni == 4 && sizeof(T) == 8 && m.pad) {
-          auto fits = [&](int64_t t) {
-            if ((t + m.ext[g - 1]) / V > (int64_t)kMultiPF * 256) return false;
-            for (int k = 0; k < g; ++k) {
-              const int64_t s = lv[j0 - 1 + k].s, M = s % V == 0 ? s / V : 0;
-              const int64_t nv = (t + (k > 0 ? m.ext[k - 1] : 0)) / V;
-              const bool blk = M == 1 || M == 2 || M == 4 || M == 8;
-              if (blk ? (nv + 4 * M - 1) / (4 * M) * M > 256 : nv > 4 * 256) return false;
-            }
-            return true;
-          };
-          int64_t t = mtile;
-          while (t >= 512 && !fits(t)) t -= 64 * V;
-          if (t >= 512) {
-            m.ni = 4;
-            m.tile = (int)t;
-            const int nvmax = (int)((t + m.ext[g - 1]) / V) + 1;
-            m.region = (nvmax + nvmax / 4 + 1) * V;  // layouts 2 / 3 add at most u/4
-          }
-        }
-        copy_taps(m.lo, lo, L);
-        copy_taps(m.hi, hi, L);
-        LaunchTimer lt(c, "inverse_level");
-        hipError_t e = launch_inverse_multi<T>(m, (int)((2 * m.region + m.slack * V) * sizeof(T)), fma, c->stream);
-        if (e != hipSuccess) return fail(VW_ERR_DEVICE, "inverse multi-level launch failed: %s", hipGetErrorString(e));
-        cur = m.out_a;
-        j = j0;
-        continue;
-      }
-      // two or three column-sweep levels per launch (k_inverse_sweep2 / 3): the intermediate
-      // approximations stay in LDS rings
-      if (tu.sweep2 && !tu.deep_inv && !tu.no_sweep && !pair && j >= 2 && has_unrolled_taps(L)) {
-        int G = 0, ka = 0, R = 0;
-        for (int levels = std::min(tu.sweep2 >= 3 ? 3 : 2, j); levels >= 2 && !G; --levels)
-          if (sweepg_plan<T>(tu, lv, j, levels, L, N, in_group, start_of, &ka, &R)) G = levels;
-        if (G) {
-          const LevelDesc& lj = lv[j - 1];
-          LevelArgs<T> a;
-          memset(&a, 0, sizeof(a));
-          a.lv = lj;
-          a.src_a = cur;
-          a.src_d = lj.use_d ? details + (size_t)(j - 1) * plane : nullptr;
-          a.use_d = lj.use_d;
-          a.thr = thr ? thr + (size_t)(j - 1) * (size_t)thr_ld : nullptr;
-          a.src_d2 = lv[j - 2].use_d ? details + (size_t)(j - 2) * plane : nullptr;
-          a.use_d2 = lv[j - 2].use_d;
-          a.thr2 = thr ? thr + (size_t)(j - 2) * (size_t)thr_ld : nullptr;
-          if (G == 3) {
-            a.src_d3 = lv[j - 3].use_d ? details + (size_t)(j - 3) * plane : nullptr;
-            a.use_d3 = lv[j - 3].use_d;
-            a.thr3 = thr ? thr + (size_t)(j - 3) * (size_t)thr_ld : nullptr;
-          }
-          a.soft = soft;
-          a.out_a = (j == G) ? y : nxt;
-          a.B = B; a.N = (int)N; a.taps = L;
-          const int kb = (G == 2 ? 2 : 4) * ka;
-          a.tile = (int)round_up(tu.sweep2_uc, kb);
-          copy_taps(a.lo, lo, L);
-          copy_taps(a.hi, hi, L);
-          LaunchTimer lt(c, "inverse_level");
-          hipError_t e = launch_inverse_sweepg<T>(a, G == 2 ? 2 : 4, ka, R, fma, c->stream);
-          if (e != hipSuccess) return fail(VW_ERR_DEVICE, "inverse level-group launch failed: %s", hipGetErrorString(e));
-          cur = a.out_a;
-          j -= G - 1;  // levels j-1 (, j-2) done too
-          continue;
-        }
-      }
-      LevelArgs<T> a;
-      memset(&a, 0, sizeof(a));
-      a.lv = lv[j - 1];
-      const int hp = (int)round_up(a.lv.hl, V);
-      const int64_t fit = ((int64_t)kLdsBytes / (int64_t)sizeof(T) / 2 - hp - a.lv.hr - 2 * V) / V * V;
-      const int tile = (int)std::min<int64_t>(tile_max, fit);
-      if (tile < 64 * V) return fail(VW_ERR_UNSUPPORTED, "level %d halo exceeds LDS", j);
-      const int64_t reg = round_up(hp + tile + a.lv.hr + V, V);
-      a.src_a = cur;
-      a.src_d = a.lv.use_d ? details + (size_t)(j - 1) * plane : nullptr;
-      a.use_d = a.lv.use_d;
-      a.out_a = (j == 1) ? y : nxt;
-      a.B = B; a.N = (int)N; a.tile = tile; a.hlpad = hp; a.hlpad_d = hp; a.region_d = (int)reg;
-      a.pair = pair; a.thr = thr ? thr + (size_t)(j - 1) * (size_t)thr_ld : nullptr; a.soft = soft; a.taps = L;
-      a.vec_io = (N % V == 0) && aligned16(a.out_a) && aligned16(a.src_a) && aligned16(a.src_d);
-      copy_taps(a.lo, lo, L);
-      copy_taps(a.hi, hi, L);
-      LaunchTimer lt(c, "inverse_level");
-      hipError_t e;
-      if (a.lv.s >= kSweepMinS && has_unrolled_taps(L) && !tu.no_sweep) {
-        a.tile = tu.sweep_qc;
-        e = launch_inverse_sweep<T>(a, fma, c->stream);
-      } else {
-        e = launch_inverse_level<T>(a, (int)(2 * reg * sizeof(T)), fma, c->stream);
-      }
-      if (e != hipSuccess) return fail(VW_ERR_DEVICE, "inverse level launch failed: %s", hipGetErrorString(e));
-      cur = a.out_a;
-    }
+    VW_TRY(forward_steps(c, k, p));
   }
-  if (ref_nf) {
-    // y alone: every non-finite level input (a_J, a kept d_j, an intermediate approximation) reaches it
-    std::vector<ScanPlane<T>> planes{{y, N, 0}};
+  if (p.ref_nf) {
+    // a_J alone: every non-finite level input (x, a_1 .. a_{J-1}, a history) reaches it (vw_ref.hip)
+    std::vector<ScanPlane<T>> planes{{k.approx, k.N, 0}};
     RefArgs<T> r;
     memset(&r, 0, sizeof(r));
-    r.x = approx_zero ? nullptr : approx; r.det_in = details; r.y = y;
-    r.thr = thr; r.thr_ld = thr_ld; r.soft = soft;
-    r.B = B; r.N = (int)N; r.J = J; r.L = L; r.mode = ref_mode(boundary);
-    copy_taps(r.lo, lo, L);
-    copy_taps(r.hi, hi, L);
-    for (int j = 0; j < J; ++j) r.lv[j] = lv[j];
-    VW_TRY(ref_nonfinite<T>(c, planes, r, true, nf_probed));
+    r.x = k.x; r.ldx = k.ldx; r.details = k.details; r.approx = k.approx;
+    r.B = k.B; r.N = (int)k.N; r.J = k.J; r.L = k.L; r.mode = ref_mode(k.boundary);
+    if (k.hist) {  // BatchStreamingMODWT block / flush: the histories the block read, and the ones it leaves
+      r.hist_mode = 1;
+      r.hist_first = k.hist_first ? 1 : 0;
+      for (int j = 0; j < k.J; ++j) {
+        r.hist_len[j] = lv[j].hist_len;
+        r.hist_old[j] = k.hist_first ? nullptr : (k.hist_update ? k.hist_snap[j] : k.hist[j]);
+        r.hist_new[j] = k.hist_update ? k.hist[j] : nullptr;
+      }
+    }
+    copy_taps(r.lo, k.lo, k.L);
+    copy_taps(r.hi, k.hi, k.L);
+    VW_TRY(ref_nonfinite<T>(c, planes, r, false, p.nf_probed, p.res.ref_grid));
   }
-  if (flags & VW_FLAG_SYNC) VW_HIP(hipStreamSynchronize(c->stream));
+  if (p.validate) {
+    unsigned long long bad = 0;
+    VW_TRY(read_bad(c, &bad));
+    VW_TRY(report_bad(bad, k.N));
+  }
+  if (k.flags & VW_FLAG_SYNC) VW_HIP(hipStreamSynchronize(c->stream));
+  return VW_OK;
+}
+
+// Per-level inverse: the plan's steps from level J down.
+template <typename T>
+static vw_status inverse_steps(vw_ctx* c, const InvCall<T>& k, const InvPlan<T>& p) {
+  const size_t plane = (size_t)k.B * (size_t)k.N;
+  T* const ws[2] = {reinterpret_cast<T*>(c->ws), reinterpret_cast<T*>(c->ws) + plane};
+  auto det = [&](int j, int use_d) { return use_d ? k.details + (size_t)(j - 1) * plane : nullptr; };
+  auto thr = [&](int j) { return k.thr ? k.thr + (size_t)(j - 1) * (size_t)k.thr_ld : nullptr; };
+  for (const PlanStep<T>& s : p.steps) {
+    const T* const src = s.src == kBufNone ? nullptr : s.src == kBufIn ? k.approx : ws[s.src - kBufWs0];
+    T* const dst = s.dst == kBufOut ? k.y : ws[s.dst - kBufWs0];
+    hipError_t e;
+    if (s.kind == kStepDeep) {
+      DeepArgs<T> d = s.deep;
+      d.src = src; d.out = dst;
+      for (int g = 0; g < d.g; ++g) {
+        d.src_d[g] = det(s.jlo + g, p.args.lv[s.jlo - 1 + g].use_d);
+        d.thr[g] = thr(s.jlo + g);
+      }
+      copy_taps(d.lo, k.lo, k.L);
+      copy_taps(d.hi, k.hi, k.L);
+      LaunchTimer lt(c, "inverse_level");
+      e = launch_deep<T>(d, s.lds, p.fma, true, c->stream);
+    } else if (s.kind == kStepMulti) {
+      MultiArgs<T> m = s.multi;
+      m.src_a = src; m.out_a = dst;
+      m.nf_flag = s.probe ? c->nf : nullptr;
+      for (int g = 0; g < m.nlev; ++g) {
+        m.src_d[g] = det(s.jlo + g, p.args.lv[s.jlo - 1 + g].use_d);
+        m.thr[g] = thr(s.jlo + g);
+      }
+      copy_taps(m.lo, k.lo, k.L);
+      copy_taps(m.hi, k.hi, k.L);
+      LaunchTimer lt(c, "inverse_level");
+      e = launch_inverse_multi<T>(m, s.lds, p.fma, c->stream);
+    } else {
+      LevelArgs<T> a = s.lvl;
+      a.src_a = src; a.out_a = dst;
+      a.src_d = det(s.jhi, a.use_d);
+      a.thr = thr(s.jhi);
+      if (s.kind == kStepSweepG) {  // the chained sweeps read the details of the levels below the top too
+        a.src_d2 = det(s.jhi - 1, a.use_d2);
+        a.thr2 = thr(s.jhi - 1);
+        if (s.jhi - s.jlo == 2) {
+          a.src_d3 = det(s.jhi - 2, a.use_d3);
+          a.thr3 = thr(s.jhi - 2);
+        }
+      }
+      copy_taps(a.lo, k.lo, k.L);
+      copy_taps(a.hi, k.hi, k.L);
+      LaunchTimer lt(c, "inverse_level");
+      e = s.kind == kStepSweepG ? launch_inverse_sweepg<T>(a, s.G, s.ka, s.R, p.fma, c->stream)
+        : s.kind == kStepSweep  ? launch_inverse_sweep<T>(a, p.fma, c->stream)
+                                : launch_inverse_level<T>(a, s.lds, p.fma, c->stream);
+    }
+    if (e != hipSuccess) return step_failed("inverse", s.kind, e);
+  }
+  return VW_OK;
+}
+
+// Inverse
+template <typename T>
+static vw_status inverse_impl(vw_ctx* c, InvCall<T> k) {
+  VW_TRY(capture_guard(c, k.flags));
+  k.cus = c->cus;
+  InvPlan<T> p;
+  plan_inverse(c->tune, k, &p);
+  if (p.error != VW_OK) return fail((vw_status)p.error, "%s", p.msg);
+  VW_TRY(reserve(c, p.res));
+  if (p.fused) {
+    InvArgs<T> a = p.args;
+    a.details = k.details; a.approx = k.approx; a.y = k.y; a.thr = k.thr;
+    a.nf_flag = p.nf_probed ? c->nf : nullptr;
+    copy_taps(a.lo, k.lo, k.L);
+    copy_taps(a.hi, k.hi, k.L);
+    LaunchTimer lt(c, "inverse");
+    hipError_t e = p.kernel == kInvMfma ? mfma_inverse(a, p.lds, c->stream)
+                                        : launch_inverse_fused<T>(a, p.threads, p.lds, p.fma, p.nv, c->stream);
+    if (e != hipSuccess) return fail(VW_ERR_DEVICE, "inverse launch failed: %s", hipGetErrorString(e));
+  } else {
+    VW_TRY(inverse_steps(c, k, p));
+  }
+  if (p.ref_nf) {
+    // y alone: every non-finite level input (a_J, a kept d_j, an intermediate approximation) reaches it
+    std::vector<ScanPlane<T>> planes{{k.y, k.N, 0}};
+    RefArgs<T> r;
+    memset(&r, 0, sizeof(r));
+    r.x = k.approx_zero ? nullptr : k.approx; r.det_in = k.details; r.y = k.y;
+    r.thr = k.thr; r.thr_ld = k.thr_ld; r.soft = k.soft;
+    r.B = k.B; r.N = (int)k.N; r.J = k.J; r.L = k.L; r.mode = ref_mode(k.boundary);
+    copy_taps(r.lo, k.lo, k.L);
+    copy_taps(r.hi, k.hi, k.L);
+    for (int j = 0; j < k.J; ++j) r.lv[j] = p.args.lv[j];
+    VW_TRY(ref_nonfinite<T>(c, planes, r, true, p.nf_probed, p.res.ref_grid));
+  }
+  if (k.flags & VW_FLAG_SYNC) VW_HIP(hipStreamSynchronize(c->stream));
   return VW_OK;
 }
 
@@ -1990,8 +1152,10 @@ static vw_status forward_host(vw_ctx* c, const T* x, int64_t B, int64_t N, int64
   VW_TRY(s.in(x, (size_t)(B - 1) * ldx + N, &dx));  // (the last row's padding need not exist)
   VW_TRY(s.in<T>(nullptr, (size_t)J * B * N, &dd));
   VW_TRY(s.in<T>(nullptr, (size_t)B * N, &da));
-  VW_TRY(forward_impl<T>(c, dx, B, N, ldx, lo, hi, L, boundary, J, flags & ~(VW_FLAG_SYNC | VW_FLAG_HOST_MEMORY), dd,
-                         da, false, -1, nullptr, false));
+  FwdCall<T> fk;
+  fk.x = dx; fk.B = B; fk.N = N; fk.ldx = ldx; fk.lo = lo; fk.hi = hi; fk.L = L; fk.boundary = boundary; fk.J = J;
+  fk.flags = flags & ~(VW_FLAG_SYNC | VW_FLAG_HOST_MEMORY); fk.details = dd; fk.approx = da;
+  VW_TRY(forward_impl<T>(c, fk));
   VW_TRY(s.out_planes(details, dd, (size_t)J, (size_t)(B * N), (size_t)det_stride));
   VW_TRY(s.out(approx, da, (size_t)B * N));
   VW_HIP(hipStreamSynchronize(c->stream));
@@ -2008,8 +1172,11 @@ static vw_status inverse_host(vw_ctx* c, const T* details, int64_t det_stride, c
   if (detail_mask) VW_TRY(s.in_planes(details, (size_t)J, (size_t)(B * N), (size_t)det_stride, &dd));
   if (!approx_zero) VW_TRY(s.in(approx, (size_t)B * N, &da));
   VW_TRY(s.in<T>(nullptr, (size_t)B * N, &dy));
-  VW_TRY(inverse_impl<T>(c, dd, da, B, N, lo, hi, L, wid, boundary, J, detail_mask, approx_zero,
-                         flags & ~(VW_FLAG_SYNC | VW_FLAG_HOST_MEMORY), dy, false, nullptr, 0));
+  InvCall<T> ik;
+  ik.details = dd; ik.approx = da; ik.B = B; ik.N = N; ik.lo = lo; ik.hi = hi; ik.L = L; ik.wid = wid;
+  ik.boundary = boundary; ik.J = J; ik.detail_mask = detail_mask; ik.approx_zero = approx_zero;
+  ik.flags = flags & ~(VW_FLAG_SYNC | VW_FLAG_HOST_MEMORY); ik.y = dy;
+  VW_TRY(inverse_impl<T>(c, ik));
   VW_TRY(s.out(y, dy, (size_t)B * N));
   VW_HIP(hipStreamSynchronize(c->stream));
   return VW_OK;
@@ -2030,7 +1197,10 @@ static vw_status modwt_forward(vw_ctx* c, const T* x, int64_t B, int64_t N, int6
     VW_TRY(forward_host<T>(c, x, B, N, ldx, lo, hi, L, boundary, J, flags, details, B * N, approx));
     return ok();
   }
-  VW_TRY(forward_impl<T>(c, x, B, N, ldx, lo, hi, L, boundary, J, flags, details, approx, false, -1, nullptr, false));
+  FwdCall<T> fk;
+  fk.x = x; fk.B = B; fk.N = N; fk.ldx = ldx; fk.lo = lo; fk.hi = hi; fk.L = L; fk.boundary = boundary; fk.J = J;
+  fk.flags = flags; fk.details = details; fk.approx = approx;
+  VW_TRY(forward_impl<T>(c, fk));
   return ok();
 }
 
@@ -2055,8 +1225,11 @@ static vw_status modwt_inverse(vw_ctx* c, const T* details, const T* approx, int
                            flags, y));
     return ok();
   }
-  VW_TRY(inverse_impl<T>(c, details, approx, B, N, lo, hi, L, wid, boundary, J, detail_mask, approx_zero, flags, y,
-                         false, nullptr, 0));
+  InvCall<T> ik;
+  ik.details = details; ik.approx = approx; ik.B = B; ik.N = N; ik.lo = lo; ik.hi = hi; ik.L = L; ik.wid = wid;
+  ik.boundary = boundary; ik.J = J; ik.detail_mask = detail_mask; ik.approx_zero = approx_zero; ik.flags = flags;
+  ik.y = y;
+  VW_TRY(inverse_impl<T>(c, ik));
   return ok();
 }
 
@@ -2250,8 +1423,10 @@ extern "C" vw_status vw_modwt1_forward_f64(vw_ctx* c, const double* x, int64_t B
       if (e != hipSuccess) return fail(VW_ERR_DEVICE, "launch failed: %s", hipGetErrorString(e));
       return VW_OK;
     }
-    return forward_impl<double>(c, dx, B, N, ldx, lo, hi, L, boundary, 1, fl & ~VW_FLAG_FFT_SWITCH, dd, da, true,
-                                -1, nullptr, false);
+    FwdCall<double> fk;
+    fk.x = dx; fk.B = B; fk.N = N; fk.ldx = ldx; fk.lo = lo; fk.hi = hi; fk.L = L; fk.boundary = boundary; fk.J = 1;
+    fk.flags = fl & ~VW_FLAG_FFT_SWITCH; fk.details = dd; fk.approx = da; fk.single_level = true;
+    return forward_impl<double>(c, fk);
   };
   if (flags & VW_FLAG_HOST_MEMORY) {
     Staging s(c);
@@ -2283,14 +1458,18 @@ extern "C" vw_status vw_modwt1_inverse_f64(vw_ctx* c, const double* approx, cons
     VW_TRY(s.in(approx, (size_t)B * N, &da));
     VW_TRY(s.in(detail, (size_t)B * N, &dd));
     VW_TRY(s.in<double>(nullptr, (size_t)B * N, &dy));
-    VW_TRY(inverse_impl<double>(c, dd, da, B, N, lo, hi, L, VW_WID_OTHER, boundary, 1, 1u, 0, flags & ~VW_FLAG_SYNC,
-                                dy, true, nullptr, 0));
+    InvCall<double> ik;
+    ik.details = dd; ik.approx = da; ik.B = B; ik.N = N; ik.lo = lo; ik.hi = hi; ik.L = L; ik.boundary = boundary;
+    ik.J = 1; ik.detail_mask = 1u; ik.flags = flags & ~VW_FLAG_SYNC; ik.y = dy; ik.single_level = true;
+    VW_TRY(inverse_impl<double>(c, ik));
     VW_TRY(s.out(y, dy, (size_t)B * N));
     VW_HIP(hipStreamSynchronize(c->stream));
     return ok();
   }
-  VW_TRY(inverse_impl<double>(c, detail, approx, B, N, lo, hi, L, VW_WID_OTHER, boundary, 1, 1u, 0, flags, y, true,
-                              nullptr, 0));
+  InvCall<double> ik;
+  ik.details = detail; ik.approx = approx; ik.B = B; ik.N = N; ik.lo = lo; ik.hi = hi; ik.L = L;
+  ik.boundary = boundary; ik.J = 1; ik.detail_mask = 1u; ik.flags = flags; ik.y = y; ik.single_level = true;
+  VW_TRY(inverse_impl<double>(c, ik));
   return ok();
 }
 
@@ -2455,10 +1634,16 @@ static vw_status wavelet_sharpe_device(vw_ctx* c, FinArgs a, const double* lo, c
   double* dd = da + plane;
   double* dy = dd + plane;
   const unsigned tf = flags & (VW_FLAG_VALIDATE | VW_FLAG_REF_NONFINITE);
-  VW_TRY(forward_impl<double>(c, a.x, a.B, a.N, a.ld, lo, hi, a.L, boundary, 1, tf, dd, da, true, -1, nullptr, false));
+  FwdCall<double> fk;
+  fk.x = a.x; fk.B = a.B; fk.N = a.N; fk.ldx = a.ld; fk.lo = lo; fk.hi = hi; fk.L = a.L; fk.boundary = boundary;
+  fk.J = 1; fk.flags = tf; fk.details = dd; fk.approx = da; fk.single_level = true;
+  VW_TRY(forward_impl<double>(c, fk));
   VW_HIP(hipMemsetAsync(dd, 0, plane * sizeof(double), c->stream));  // `new double[detailCoeffs.length]`
-  VW_TRY(inverse_impl<double>(c, dd, da, a.B, a.N, lo, hi, a.L, VW_WID_OTHER, boundary, 1, 1u, 0,
-                              tf & ~VW_FLAG_VALIDATE, dy, true, nullptr, 0));
+  InvCall<double> ik;
+  ik.details = dd; ik.approx = da; ik.B = a.B; ik.N = a.N; ik.lo = lo; ik.hi = hi; ik.L = a.L;
+  ik.boundary = boundary; ik.J = 1; ik.detail_mask = 1u; ik.flags = tf & ~VW_FLAG_VALIDATE; ik.y = dy;
+  ik.single_level = true;
+  VW_TRY(inverse_impl<double>(c, ik));
   a.x = dy;
   a.ld = a.N;
   return fin_launch(c, a, false, flags);
@@ -2608,8 +1793,10 @@ static vw_status denoise_device(vw_ctx* c, const double* x, int64_t B, int64_t N
   double* app = det + (size_t)J * plane;
   double* thr = reinterpret_cast<double*>(reinterpret_cast<char*>(buf) +
                                           align_up(((size_t)J + 1) * plane * sizeof(double), 256));
-  vw_status st = forward_impl<double>(c, x, B, N, ldx, lo, hi, L, boundary, J, flags & ~VW_FLAG_SYNC, det, app, false,
-                                      -1, nullptr, false);
+  FwdCall<double> fk;
+  fk.x = x; fk.B = B; fk.N = N; fk.ldx = ldx; fk.lo = lo; fk.hi = hi; fk.L = L; fk.boundary = boundary; fk.J = J;
+  fk.flags = flags & ~VW_FLAG_SYNC; fk.details = det; fk.approx = app;
+  vw_status st = forward_impl<double>(c, fk);
   if (st == VW_OK) {
     hipError_t e = hipSuccess;
     if (threshold < 0) {
@@ -2626,9 +1813,12 @@ static vw_status denoise_device(vw_ctx* c, const double* x, int64_t B, int64_t N
     }
     if (e != hipSuccess) st = fail(VW_ERR_DEVICE, "threshold stage failed: %s", hipGetErrorString(e));
   }
-  if (st == VW_OK)
-    st = inverse_impl<double>(c, det, app, B, N, lo, hi, L, wid, boundary, J, ~0u, 0, flags & ~VW_FLAG_SYNC, y, false,
-                              thr, soft);
+  if (st == VW_OK) {
+    InvCall<double> ik;
+    ik.details = det; ik.approx = app; ik.B = B; ik.N = N; ik.lo = lo; ik.hi = hi; ik.L = L; ik.wid = wid;
+    ik.boundary = boundary; ik.J = J; ik.flags = flags & ~VW_FLAG_SYNC; ik.y = y; ik.thr = thr; ik.soft = soft;
+    st = inverse_impl<double>(c, ik);
+  }
   if (st == VW_OK && thr_out) {
     hipError_t e = hipMemcpyAsync(thr_out, thr, (size_t)B * sizeof(double), hipMemcpyDeviceToDevice, c->stream);
     if (e != hipSuccess) st = fail(VW_ERR_DEVICE, "copy failed");
@@ -2694,10 +1884,11 @@ static vw_status wavelet_denoise_device(vw_ctx* c, const double* x, int64_t B, i
   double* sig = reinterpret_cast<double*>(reinterpret_cast<char*>(c->ws2) + coef_bytes);
   double* thr = reinterpret_cast<double*>(reinterpret_cast<char*>(sig) + align_up((size_t)B * 8, 256));
   const unsigned fl = flags & ~VW_FLAG_SYNC;
-  vw_status st = levels > 0 ? forward_impl<double>(c, x, B, N, ldx, lo, hi, L, boundary, J, fl, det, app, false, -1,
-                                                   nullptr, false)
-                            : forward_impl<double>(c, x, B, N, ldx, lo, hi, L, boundary, 1, fl & ~VW_FLAG_FFT_SWITCH,
-                                                   det, app, true, -1, nullptr, false);
+  FwdCall<double> fk;
+  fk.x = x; fk.B = B; fk.N = N; fk.ldx = ldx; fk.lo = lo; fk.hi = hi; fk.L = L; fk.boundary = boundary;
+  fk.J = levels > 0 ? J : 1; fk.flags = levels > 0 ? fl : fl & ~VW_FLAG_FFT_SWITCH; fk.details = det; fk.approx = app;
+  fk.single_level = levels <= 0;
+  vw_status st = forward_impl<double>(c, fk);
   if (st != VW_OK) return st;
   hipError_t e = hipSuccess;
   if (method == kThrFixed) {
@@ -2723,10 +1914,15 @@ static vw_status wavelet_denoise_device(vw_ctx* c, const double* x, int64_t B, i
     }
   }
   if (e != hipSuccess) return fail(VW_ERR_DEVICE, "threshold stage failed: %s", hipGetErrorString(e));
-  if (levels > 0)
-    st = inverse_impl<double>(c, det, app, B, N, lo, hi, L, wid, boundary, J, ~0u, 0, fl, y, false, thr, soft, B);
-  else
-    st = inverse_impl<double>(c, det, app, B, N, lo, hi, L, VW_WID_OTHER, boundary, 1, 1u, 0, fl, y, true, thr, soft);
+  InvCall<double> ik;
+  ik.details = det; ik.approx = app; ik.B = B; ik.N = N; ik.lo = lo; ik.hi = hi; ik.L = L; ik.boundary = boundary;
+  ik.flags = fl; ik.y = y; ik.thr = thr; ik.soft = soft;
+  if (levels > 0) {
+    ik.wid = wid; ik.J = J; ik.thr_ld = B;
+  } else {
+    ik.J = 1; ik.detail_mask = 1u; ik.single_level = true;
+  }
+  st = inverse_impl<double>(c, ik);
   if (st == VW_OK && thr_out) {
     e = hipMemcpyAsync(thr_out, thr, (size_t)J * B * sizeof(double), hipMemcpyDeviceToDevice, c->stream);
     if (e != hipSuccess) st = fail(VW_ERR_DEVICE, "copy failed");
@@ -2902,14 +2098,20 @@ static vw_status stream_run(vw_stream* s, const double* blk, int64_t B, int64_t 
   vw_ctx* c = s->ctx;
   if (s->boundary == VW_PERIODIC) {
     // processMultiLevel PERIODIC -> BatchMODWT.multiLevelAoS (no cap), BatchStreamingMODWT.java:115-116
-    return forward_impl<double>(c, blk, B, n, n, s->lo.data(), s->hi.data(), s->L, s->boundary, s->levels,
-                                flags & ~VW_FLAG_SYNC, details, approx, false, -1, nullptr, false);
+    FwdCall<double> fk;
+    fk.x = blk; fk.B = B; fk.N = n; fk.ldx = n; fk.lo = s->lo.data(); fk.hi = s->hi.data(); fk.L = s->L;
+    fk.boundary = s->boundary; fk.J = s->levels; fk.flags = flags & ~VW_FLAG_SYNC; fk.details = details;
+    fk.approx = approx;
+    return forward_impl<double>(c, fk);
   }
   const bool first = !s->hist_init;
   const int mode = first ? -1 : kHaloHistory;
-  return forward_impl<double>(c, blk, B, n, n, s->lo.data(), s->hi.data(), s->L, s->boundary, s->levels,
-                              flags & ~VW_FLAG_SYNC, details, approx, false, mode, s->hist.data(), !flush,
-                              s->snap[0] ? s->snap.data() : nullptr, first);
+  FwdCall<double> fk;
+  fk.x = blk; fk.B = B; fk.N = n; fk.ldx = n; fk.lo = s->lo.data(); fk.hi = s->hi.data(); fk.L = s->L;
+  fk.boundary = s->boundary; fk.J = s->levels; fk.flags = flags & ~VW_FLAG_SYNC; fk.details = details;
+  fk.approx = approx; fk.mode_override = mode; fk.hist = s->hist.data(); fk.hist_update = !flush;
+  fk.hist_snap = s->snap[0] ? s->snap.data() : nullptr; fk.hist_first = first;
+  return forward_impl<double>(c, fk);
 }
 
 extern "C" vw_status vw_stream_process_f64(vw_stream* s, const double* block, int64_t B, int64_t n, unsigned flags,
@@ -2989,9 +2191,11 @@ extern "C" vw_status vw_stream_flush_f64(vw_stream* s, int64_t tail_len, unsigne
     VW_TRY(sg.in<double>(nullptr, (size_t)s->levels * B * tail_len, &dd));
     VW_TRY(sg.in<double>(nullptr, (size_t)B * tail_len, &da));
   }
-  VW_TRY(forward_impl<double>(c, dt, B, tail_len, tail_len, s->lo.data(), s->hi.data(), s->L, s->boundary, s->levels,
-                              flags & ~VW_FLAG_SYNC, host ? dd : details, host ? da : approx, false, kHaloHistory,
-                              s->hist.data(), false));
+  FwdCall<double> fk;
+  fk.x = dt; fk.B = B; fk.N = tail_len; fk.ldx = tail_len; fk.lo = s->lo.data(); fk.hi = s->hi.data(); fk.L = s->L;
+  fk.boundary = s->boundary; fk.J = s->levels; fk.flags = flags & ~VW_FLAG_SYNC; fk.details = host ? dd : details;
+  fk.approx = host ? da : approx; fk.mode_override = kHaloHistory; fk.hist = s->hist.data();
+  VW_TRY(forward_impl<double>(c, fk));
   if (host) {
     VW_TRY(sg.out(details, dd, (size_t)s->levels * B * tail_len));
     VW_TRY(sg.out(approx, da, (size_t)B * tail_len));

@@ -371,7 +371,7 @@ __device__ __forceinline__ void inv_pair(const T* A, const T* D, int t0, int S, 
 // runtime checks (bounds, modes, spacing, direction) cost several SALU + a branch each.  So the
 // fused kernels make every such decision once per level (row functions below, templated on the
 // spacing class and direction), and only the last of a thread's NV vectors carries a bounds check:
-// the host sizes the workgroup so that slabs 0..NV-2 are full ((NV-1)*NT <= nvec, vw_capi.cpp).
+// the host sizes the workgroup so that slabs 0..NV-2 are full ((NV-1)*NT <= nvec, vw_plan.cpp fused_plan).
 // FULL: every slab is full (threads * NV == nvec, a host contract): no bounds check at all.
 template <int L, int NV, bool FULL = false, typename F>
 __device__ __forceinline__ void for_vecs(int nvec, F&& fn) {
@@ -931,7 +931,7 @@ __global__ void VW_FUSED_BOUNDS(NV, VW_FUSED_W(L, 8)) k_forward_fused(const FwdA
 // LDS reads of level J (it cannot prove the buffers disjoint).  Completion is waited for explicitly:
 // vmcnt counts a wave's vector-memory operations in issue order, and exactly 2*NV stores (detail +
 // approximation rows) follow the DMA, so vmcnt(2*NV) retires the DMA and leaves those stores in
-// flight.  Host contract (vw_capi.cpp): two buffers, every slab full (threads*NV == N/V), whole
+// flight.  Host contract (vw_plan.cpp plan_forward_fused): two buffers, every slab full (threads*NV == N/V), whole
 // waves, N/V a multiple of 64 (one wave instruction = 64 x 16 B), no validation, no history.
 // One wave instruction of LDS-DMA: 64 lanes x 16 bytes from per-lane global addresses into 1 KiB of
 // LDS at the wave-uniform byte address `lds` (global_load_lds_dwordx4; no VGPR is written).  nt: the
@@ -1583,7 +1583,7 @@ __device__ __forceinline__ void blk_fwd(const T* X, const BlkLayout& lo, int HLV
 
 // blk_fwd with wave-uniform offsets (as blk_inv_branch_s): Xb = X + blk_phys(layout, vb + HLV) * V, and the
 // read of logical vector vb + HLV + q*m sits off(q) = q*m + ((q*m) >> sh)*pad from it for every thread
-// when the pad groups align with a thread's block and HLV is a multiple of the group (host: vw_capi.cpp
+// when the pad groups align with a thread's block and HLV is a multiple of the group (host: vw_plan.cpp blk_plan
 // rounds HLV up to 16 vectors); q*m < 0 shifts arithmetically (floor), as blk_phys does.
 template <typename T, int L, bool FMA, int NV>
 __device__ __forceinline__ void blk_fwd_s(const T* Xb, int m, int sh, int pad, const T* flo, const T* fhi,
@@ -2253,7 +2253,7 @@ __global__ void __launch_bounds__(256) k_inverse_sweep(const LevelArgs<T> p) {
 // One barrier per step; every ring holds three blocks.  The upper stages run past the chunk by their
 // reach (L-1 positions at each level below, <= KB) and wrap mod N: every value equals the reference's
 // (t+l)%N read, products summed in the same order -> bit-exact in EXACT mode.
-// Host contract (vw_capi.cpp): h % R == 0, N % (G*h) == 0, every level PERIODIC / dir +1 / offset 0,
+// Host contract (vw_plan.cpp sweepg_plan): h % R == 0, N % (G*h) == 0, every level PERIODIC / dir +1 / offset 0,
 // (2*KB + 2*L) * G*h <= N (one wrap at most), KB >= 2*(L-1), p.tile (u per chunk) a multiple of KB.
 
 // KA outputs of one level at u = ub + st*k (k < KA, st = the level's spacing in u): a from an LDS ring
@@ -2472,7 +2472,7 @@ __global__ void __launch_bounds__(12 * R) k_inverse_sweep3(const LevelArgs<T> p)
 }
 
 // ---------------------------------------------------------------------------------------------
-// Multi-level tiles for long PERIODIC signals (host: vw_capi.cpp level_groups).  One workgroup runs
+// Multi-level tiles for long PERIODIC signals (host: vw_plan.cpp level_groups).  One workgroup runs
 // a group of consecutive levels over one tile of one signal; the intermediate approximations stay
 // in LDS.  Periodic convolution commutes with shifts, so a level evaluated at a position v outside
 // [0, N) (the tile's halo) equals the reference's value at v mod N bit for bit -- the same products

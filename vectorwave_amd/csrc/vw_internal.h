@@ -1,9 +1,10 @@
-// vw_internal.h -- shared between the HIP kernels (vw_kernels.hip) and the C-ABI host layer
-// (vw_capi.cpp).  Not installed; the public boundary is include/vectorwave_amd.h.
+// vw_internal.h -- shared between the HIP kernels (vw_kernels.hip), the planner (vw_plan.cpp) and the
+// C-ABI host layer (vw_capi.cpp).  Not installed; the public boundary is include/vectorwave_amd.h.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <atomic>
 #include <cstdint>
+#include "vw_taps.h"
 
 namespace vw {
 
@@ -24,7 +25,7 @@ enum HaloMode : int {
   kHaloHistory = 4     // streaming left history   BatchSIMDMODWT.java:447-507
 };
 
-// Per-level description, computed on the host (vw_capi.cpp) from the reference's bookkeeping.
+// Per-level description, computed on the host (vw_plan.cpp forward_levels / inverse_levels) from the reference's bookkeeping.
 struct LevelDesc {
   int s;        // a-trous spacing 2^(j-1)
   int hl, hr;   // halo extents (elements) the level reads left of 0 / right of N-1
@@ -54,12 +55,12 @@ struct FwdArgs {
   int hlpad;            // LDS offset of element 0 (multiple of the vector width)
   int region1;          // element offset of the second level buffer (0 = single buffer)
   int vec_io;
-  int unrolled;         // 1: the tap-unrolled kernel may run (aligned rows, full slabs; vw_capi fused_plan)
+  int unrolled;         // 1: the tap-unrolled kernel may run (aligned rows, full slabs; vw_plan.cpp fused_plan)
   int dma_nt;           // k_forward_persist: non-temporal LDS-DMA of the signal rows
   int level_ct;         // 1: strided levels of short filters dispatch to compile-time-stride bodies, and
                         // k_forward_persist runs its full-slab form (VW_LEVEL_CT; vw_device.h fwd_row_ct)
   int validate;         // 1: non-finite check on input and outputs (atomicMin into *bad)
-  int rev;              // 1: workgroup g owns signal B-1-g (walk order, see vw_capi.cpp walk_reverse)
+  int rev;              // 1: workgroup g owns signal B-1-g (walk order: VW_FWD_REV, vw_plan.h Tuning)
   unsigned long long* bad;
   // streaming history (kHaloHistory): hist[j] is [B][hist_len_j], oldest first
   T* hist[kMaxLevels];
@@ -237,10 +238,7 @@ template <typename T>
 hipError_t launch_ref_cascade(const RefArgs<T>& a, int grid, bool inverse, hipStream_t st);
 int ref_scan_chunks(int N);
 
-// Matrix-core fp32 kernels (vw_mfma.hip): which (L, N) are instantiated, the halo a level set needs, launchers.
-bool mfma_supported(int L, long long N);
-int mfma_halo(int L, int J);
-int mfma_region(int n);  // LDS floats of the kernels' padded level region for elements [0, n)
+// Matrix-core fp32 kernels (vw_mfma.hip); mfma_supported / mfma_halo / mfma_region: vw_taps.h
 hipError_t launch_forward_mfma(const FwdArgs<float>& a, int lds, hipStream_t st);
 hipError_t launch_inverse_mfma(const InvArgs<float>& a, int lds, hipStream_t st);
 
@@ -350,8 +348,6 @@ inline void blk_layout_host(int m, int nv, int* sh, int* pad, int tight = 0) {
   else { *sh = 2; *pad = 1; }
 }
 
-// Which compile-time tap counts have unrolled kernels; others use the runtime-L kernel.
-bool has_unrolled_taps(int L);
 int fused_max_threads();
 
 }  // namespace vw

@@ -84,7 +84,7 @@ template hipError_t launch_inverse_sweep<VW_T>(const LevelArgs<VW_T>&, bool, hip
 // Two / three inverse levels per launch (k_inverse_sweep2 / k_inverse_sweep3): one workgroup per (signal,
 // R-residue block, u-chunk) of 4R / 12R threads.  KA = 8 or 16 outputs per thread and step; a block
 // (G*KA positions) must cover the reach of the levels below the top, and the rings must fit LDS
-// (the host applies the same rule: vw_capi.cpp sweepg_plan).
+// (the host applies the same rule: vw_plan.cpp sweepg_plan).
 template <typename T, int L, bool FMA, int KA, int R, int G>
 static hipError_t run_inverse_sweepg(const LevelArgs<T>& a, hipStream_t st) {
   constexpr int KMIN = (G == 2 ? 1 : 2) * (L - 1);

@@ -26,7 +26,7 @@
 //
 // Scope: PERIODIC, fp32, VW_FLAG_FMA (EXACT keeps the VALU kernels: separate multiply and add), one signal
 // per workgroup (NT threads, N = 4 * NT * TPW samples, TPW tiles per wave), every level's halo (4*KS - 16)*s
-// within the row.  Host policy: vw_capi.cpp (VW_MFMA).
+// within the row.  Host policy: vw_plan.cpp mfma_layout (VW_MFMA).
 #include "vw_device.h"
 
 namespace vw {
@@ -89,9 +89,7 @@ __device__ __forceinline__ void put_tile(float* sc, int lane, float* __restrict_
 // padded, the modelled B reads are conflict-free at s <= 4 and 2-way above, and -- what keeps them one
 // ds_read at an offset -- the slot distance ph(i0 -+ 4*s*q) - ph(i0) of k-step q is the same for every lane
 // and tile of a level (dq below, computed once per level).
-#ifndef VW_MFMA_PAD_SHIFT
-#define VW_MFMA_PAD_SHIFT 3
-#endif
+// (VW_MFMA_PAD_SHIFT: vw_taps.h, shared with the host planner's mfma_region)
 __device__ __forceinline__ int ph(int i) { return i + (i >> VW_MFMA_PAD_SHIFT); }
 
 // Forward, PERIODIC, fp32 FMA: all J levels of one signal per workgroup.  One LDS level buffer X: element t
@@ -352,15 +350,7 @@ static hipError_t run_inv(const InvArgs<float>& a, int lds, hipStream_t st) {
     default: return hipErrorNotSupported;                                    \
   }
 
-bool mfma_supported(int L, long long N) {
-  return (L == 30 || L == 16) && (N == 2048 || N == 4096 || N == 8192);
-}
-
-int mfma_halo(int L, int J) { return (4 * ((L + 15 + 3) / 4) - 16) << (J - 1); }
-
-// LDS floats of the padded level region of elements [0, n) (the tap table follows it)
-int mfma_region(int n) { return n == 0 ? 0 : (n - 1) + ((n - 1) >> VW_MFMA_PAD_SHIFT) + 1; }
-
+// (mfma_supported / mfma_halo / mfma_region, the host's view of this table: vw_taps.h)
 hipError_t launch_forward_mfma(const FwdArgs<float>& a, int lds, hipStream_t st) { VW_MFMA_DISPATCH(run_fwd, a, lds, st) }
 hipError_t launch_inverse_mfma(const InvArgs<float>& a, int lds, hipStream_t st) { VW_MFMA_DISPATCH(run_inv, a, lds, st) }
 

@@ -5,24 +5,6 @@
 
 namespace vw {
 
-// Unrolled tap counts; other L use the runtime-L kernels.  Dev builds may restrict the list:
-// make DEV_TAPS='X(8)' (the runtime-L kernel still covers every other L).
-#ifdef VW_DEV_TAPS
-#define VW_TAP_LIST(X) VW_DEV_TAPS(X)
-#else
-#define VW_TAP_LIST(X) X(2) X(4) X(6) X(8) X(10) X(12) X(14) X(16) X(18) X(20) X(24) X(30)
-#endif
-
-
-bool has_unrolled_taps(int L) {
-  switch (L) {
-#define VW_CASE(n) case n: return true;
-    VW_TAP_LIST(VW_CASE)
-#undef VW_CASE
-    default: return false;
-  }
-}
-
 int fused_max_threads() { return kMaxThreads; }
 
 template <typename T>

@@ -10,7 +10,7 @@ static hipError_t run_multi(const MultiArgs<T>& a, int lds, hipStream_t st) {
   static LdsOnce configured, configured4;
   LdsOnce* once = &configured;
   if constexpr (INV && sizeof(T) == 8) {
-    if (a.ni == 4) {  // four output vectors per thread (host: vw_capi.cpp multi_inv_ni)
+    if (a.ni == 4) {  // four output vectors per thread (host: vw_plan.cpp inverse_multi_layout)
       k = k_inverse_multi<T, L, FMA, 4>;
       once = &configured4;
     }
