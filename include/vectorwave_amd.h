@@ -35,6 +35,8 @@
  *                             (fin/ = vectorwave-core/src/main/java/com/morphiqlabs/financial/)
  *   vw_fin_sharpe_*         FinancialWaveletAnalyzer.calculateSharpeRatio  fin/FinancialWaveletAnalyzer.java:95-124
  *   vw_fin_wavelet_sharpe_* FinancialWaveletAnalyzer.calculateWaveletSharpeRatio  fin/FinancialWaveletAnalyzer.java:166-212
+ *   vw_modwt_energy_f64 /   MultiLevelMODWTResult.getDetailEnergyAtLevel / getApproximationEnergy / getTotalEnergy /
+ *   vw_energy_planes_f64      getRelativeEnergyDistribution  core/modwt/MultiLevelMODWTResultImpl.java:91-139, :211-216
  *   vw_max_levels           MultiLevelMODWTTransform.getMaximumLevels  core/modwt/MultiLevelMODWTTransform.java:455-501, :693-695
  *   status codes            core/exception/ErrorCode.java:24-118 (see the table below)
  *
@@ -143,8 +145,8 @@ enum {
      * (BatchSIMDMODWT.generalBatchMODWTSoAWithScaledFiltersAndHistory :447-507) multiplies every tap, and
      * the recomputed rows rewrite the histories they leave for the next block. */
     VW_FLAG_REF_NONFINITE = 1u << 8,
-    /* Financial calls (vw_fin_*): every sum may be a wave / workgroup tree reduction instead of the
-     * reference's sequential loop.  Default (flag clear): one lane adds in index order, bit-identical to
+    /* Financial and energy calls (vw_fin_*, vw_modwt_energy_f64, vw_energy_planes_f64): every sum may be a
+     * wave / workgroup tree reduction instead of the reference's sequential loop.  Default (flag clear): one lane adds in index order, bit-identical to
      * com.morphiqlabs.financial; the dependent fp64 adds of that walk then bound the call.  The
      * convolution stays EXACT either way. */
     VW_FLAG_TREE_SUMS = 1u << 9
@@ -202,6 +204,36 @@ VW_API vw_status vw_modwt_inverse_f32(vw_ctx *ctx, const float *details, const f
                                       int64_t B, int64_t N, const double *lo, const double *hi, int L,
                                       int wavelet_id, int boundary, int J, unsigned detail_mask,
                                       int approx_zero, unsigned flags, float *y);
+
+/* ---- wavelet energy per level --------------------------------------------------------------------
+ * MultiLevelMODWTResult.getApproximationEnergy / getDetailEnergyAtLevel / getRelativeEnergyDistribution
+ * (core/modwt/MultiLevelMODWTResultImpl.java:91-139, computeEnergy :211-216; MutableMultiLevelMODWTResultImpl
+ * .java:143-208) for a batch.  out is [J+1][B] (the memory kind of the other arrays): out[0][b] the approximation
+ * energy of signal b, out[j][b] the detail energy of level j -- getRelativeEnergyDistribution's order.  fp64 only:
+ * the reference's energies are double sums of double coefficients.
+ *
+ * vw_modwt_energy_f64 takes vw_modwt_forward_f64's arguments, makes the same checks with the same statuses and
+ * vw_last_error_index(), and sums the squares of the coefficients that call produces with the same flags:
+ *   default             `energy = 0.0; for c: energy += c * c` in index order, a rounded square then a rounded
+ *                       add: without VW_FLAG_FMA the reference's decompose(...) + computeEnergy bit for bit.
+ *                       Exactness costs the plane traffic: the forward writes its (J+1)*B*N coefficients into
+ *                       the context workspace and vw_energy_planes_f64's chain walk reads them back.
+ *   VW_FLAG_TREE_SUMS   per-thread partials and fixed-order wave / workgroup trees: deterministic (the same call
+ *                       gives the same bits), within N * 2^-52 relative of the sequential sum.  Where the fused
+ *                       forward's cascade fits (and without VALIDATE / REF_NONFINITE / an FFT-switch level) one
+ *                       launch reads x once and writes only out: no coefficient goes to HBM.  Elsewhere the
+ *                       forward into the workspace, then the tree sums over its planes.
+ *   VW_FLAG_FMA         affects the convolution only.
+ * vw_energy_planes_f64 sums planes already in memory (details [J][B][N], approx [B][N]; J = 0: approx alone,
+ * details may be NULL); flags: TREE_SUMS, HOST_MEMORY, SYNC.
+ * Without HOST_MEMORY / VALIDATE / SYNC both calls can be recorded into a vw_graph once a call of that shape
+ * has run (the workspace grows outside a capture only).  Context option VW_ENERGY_FUSED=0 keeps
+ * vw_modwt_energy_f64 off the fused kernel. */
+VW_API vw_status vw_modwt_energy_f64(vw_ctx *ctx, const double *x, int64_t B, int64_t N, int64_t ldx,
+                                     const double *lo, const double *hi, int L, int wavelet_id,
+                                     int boundary, int J, unsigned flags, double *out);
+VW_API vw_status vw_energy_planes_f64(vw_ctx *ctx, const double *details, const double *approx, int64_t B,
+                                      int64_t N, int J, unsigned flags, double *out);
 
 /* ---- one batch over several contexts (one host thread per context) ----------------------------
  * Replaces the reference's in-process parallelism over one batch call: BatchMODWT.multiLevelAoS /

@@ -68,6 +68,28 @@ public final class AmdBatchMODWT {
         return new BatchMODWT.MultiLevelResult(details, approx);
     }
 
+    /**
+     * Energy per level of {@code multiLevelAoS(wavelet, signals, levels)} for every signal, without the
+     * coefficients: {@code [batch][levels + 1]} in {@code [approx, d1..dJ]} order (batch semantics: no level cap;
+     * sequential sums, the reference's bits over multiLevelAoS's arrays).
+     */
+    public static double[][] energyBatch(DiscreteWavelet wavelet, double[][] signals, int levels) {
+        if (levels < 1) throw new IllegalArgumentException("levels must be >= 1");
+        validateAoS(signals);
+        final int batch = signals.length;
+        checkBatchReach(wavelet, signals[0].length, levels);
+        double[] flat = new double[Math.multiplyExact(levels + 1, batch)];
+        AmdNative.check(AmdNative.modwtEnergyAoS(AmdRuntime.ctx(), signals, wavelet.lowPassDecomposition(),
+                wavelet.highPassDecomposition(), AmdNative.waveletId(wavelet), 0, levels,
+                AmdRuntime.FMA | AmdNative.FLAG_REF_NONFINITE, flat));
+        return AmdMultiLevelMODWT.perSignal(flat, levels + 1, batch);
+    }
+
+    /** getRelativeEnergyDistribution (MultiLevelMODWTResultImpl :121-138) of every signal. */
+    public static double[][] relativeEnergyBatch(DiscreteWavelet wavelet, double[][] signals, int levels) {
+        return AmdMultiLevelMODWT.relative(energyBatch(wavelet, signals, levels));
+    }
+
     /** BatchMODWT.inverseSingleLevelAoS (:121-139): core MODWTTransform.inverse per signal (pairwise sums). */
     public static double[][] inverseSingleLevelAoS(DiscreteWavelet wavelet, double[][] approx, double[][] detail) {
         validateAoS(approx);

@@ -97,6 +97,51 @@ public final class AmdMultiLevelMODWT {
         return out;
     }
 
+    /**
+     * Energy per level of {@code decompose(signals[b], levels)} for every signal, without the coefficients:
+     * {@code [B][levels + 1]} in getRelativeEnergyDistribution's order {@code [approx, d1..dJ]}
+     * (MultiLevelMODWTResultImpl :91-117, computeEnergy :211-216; sequential sums, the reference's bits).
+     * Validation as decomposeBatch, by the engine.
+     */
+    public double[][] energyBatch(double[][] signals, int levels) {
+        final int n = equalRows(signals);
+        final int batch = signals.length;
+        double[] flat = new double[Math.multiplyExact(levels + 1, batch)];
+        final int flags = AmdNative.FLAG_CORE_LEVELS | AmdNative.FLAG_VALIDATE | AmdNative.FLAG_FFT_SWITCH
+                | AmdRuntime.FMA;
+        AmdNative.check(AmdNative.modwtEnergyAoS(AmdRuntime.ctx(), signals, wavelet.lowPassDecomposition(),
+                wavelet.highPassDecomposition(), AmdNative.waveletId(wavelet), boundary, levels, flags, flat));
+        return perSignal(flat, levels + 1, batch);
+    }
+
+    /** getRelativeEnergyDistribution (:121-138) of every signal: {@code [B][levels + 1]}. */
+    public double[][] relativeEnergyBatch(double[][] signals, int levels) {
+        return relative(energyBatch(signals, levels));
+    }
+
+    /** flat [planes][batch] -> [batch][planes] */
+    static double[][] perSignal(double[] flat, int planes, int batch) {
+        double[][] out = new double[batch][planes];
+        for (int k = 0; k < planes; k++) {
+            for (int b = 0; b < batch; b++) out[b][k] = flat[k * batch + b];
+        }
+        return out;
+    }
+
+    /** total = approx; total += d_1 .. d_J; each energy / total; all zeros when total == 0.0 (:121-138). */
+    static double[][] relative(double[][] energies) {
+        double[][] out = new double[energies.length][];
+        for (int b = 0; b < energies.length; b++) {
+            final double[] e = energies[b];
+            double total = e[0];
+            for (int j = 1; j < e.length; j++) total += e[j];
+            out[b] = new double[e.length];
+            if (total == 0.0) continue;
+            for (int j = 0; j < e.length; j++) out[b][j] = e[j] / total;
+        }
+        return out;
+    }
+
     /** reconstruct (:339-349): the cascade J..1. */
     public double[] reconstruct(MultiLevelMODWTResult result) {
         if (result == null) throw new NullPointerException("result cannot be null");

@@ -104,6 +104,12 @@ public final class AmdNative {
     static native int swtDenoiseAoS(long ctx, double[][] x, double[] lo, double[] hi, int waveletId, int boundary,
                                     int J, double threshold, boolean soft, int flags, double[][] y);
 
+    // energy per level of every signal (out: (levels + 1) * B doubles, [approx, d1..dJ][B]): of the forward of the
+    // rows, and of coefficient planes the caller already has (details [J][B][N], approx [B][N])
+    static native int modwtEnergyAoS(long ctx, double[][] rows, double[] lo, double[] hi, int waveletId, int boundary,
+                                     int levels, int flags, double[] out);
+    static native int energyPlanesAoS(long ctx, double[][][] details, double[][] approx, int flags, double[] out);
+
     // com.morphiqlabs.financial: FinancialAnalyzer's four metrics + the detail standard deviation of every price
     // row (out: 5 * B doubles, [5][B]); FinancialWaveletAnalyzer's Sharpe ratios of every return row (out: B)
     static native int finAnalyzeAoS(long ctx, double[][] prices, double[] lo, double[] hi, double anomalyK, int flags,

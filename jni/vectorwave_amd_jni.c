@@ -618,6 +618,73 @@ JNIEXPORT jint JNICALL VW_JNI(finAnalyzeAoS)(JNIEnv *e, jclass c, jlong ctx, job
   return st;
 }
 
+/* ---- wavelet energy per level: double[][] rows in, out = (J+1) * B doubles, [approx, d1..dJ][B] ----
+ * Row chunks like the other AoS natives: a chunk's [J+1][nb] result is scattered into columns b0 .. b0+nb of the
+ * caller's [J+1][B]; vw_set_signal_base per chunk, so a validation error names the batch's signal. */
+JNIEXPORT jint JNICALL VW_JNI(modwtEnergyAoS)(JNIEnv *e, jclass c, jlong ctx, jobjectArray x, jdoubleArray lo,
+                                              jdoubleArray hi, jint wid, jint boundary, jint J, jint flags,
+                                              jdoubleArray out) {
+  (void)c;
+  Taps tl, th;
+  if (!get_taps(e, lo, hi, &tl, &th)) return VW_ERR_ARG;
+  if (J < 1) return arg_error(e, "levels must be >= 1");
+  const jsize N = row_len(e, x);
+  if (N < 1) return VW_ERR_ARG;
+  const jsize B = (*e)->GetArrayLength(e, x);
+  if (!fin_out_ok(e, out, ((size_t)J + 1) * (size_t)B)) return VW_ERR_ARG;
+  const jsize CB = chunk_rows((size_t)N + (size_t)J + 1, B);
+  int oom = 0;
+  double *px = out_buf(0, (size_t)CB * N, &oom), *po = out_buf(1, ((size_t)J + 1) * CB, &oom);
+  if (oom) return oom_error(e);
+  vw_status st = VW_OK;
+  for (jsize b0 = 0; b0 < B && st == VW_OK; b0 += CB) {
+    const jsize nb = B - b0 < CB ? B - b0 : CB;
+    if (!gather_rows(e, x, b0, nb, N, px)) { st = VW_ERR_ARG; break; }
+    vw_set_signal_base(b0);
+    st = vw_modwt_energy_f64(CTX(ctx), px, nb, N, N, tl.v, th.v, tl.n, wid, boundary, J,
+                             (unsigned)flags | HOST_FLAGS, po);
+    vw_set_signal_base(0);
+    for (jsize k = 0; k <= J && st == VW_OK; ++k)  /* chunk plane k -> out[k][b0 .. b0+nb) */
+      (*e)->SetDoubleArrayRegion(e, out, k * B + b0, nb, po + (size_t)k * nb);
+  }
+  trim_slots();
+  return st;
+}
+
+/* details double[J][B][N], approx double[B][N] -> out (J+1) * B */
+JNIEXPORT jint JNICALL VW_JNI(energyPlanesAoS)(JNIEnv *e, jclass c, jlong ctx, jobjectArray details,
+                                               jobjectArray approx, jint flags, jdoubleArray out) {
+  (void)c;
+  const jsize N = row_len(e, approx);
+  if (N < 1) return VW_ERR_ARG;
+  const jsize B = (*e)->GetArrayLength(e, approx);
+  if (!details) return null_error(e, "details cannot be null");
+  const jsize J = (*e)->GetArrayLength(e, details);
+  if (!planes_ok(e, details, J, B)) return VW_ERR_ARG;
+  if (!fin_out_ok(e, out, ((size_t)J + 1) * (size_t)B)) return VW_ERR_ARG;
+  const jsize CB = chunk_rows(((size_t)J + 1) * ((size_t)N + 1), B);
+  int oom = 0;
+  double *pa = out_buf(0, (size_t)CB * N, &oom), *pd = out_buf(1, (size_t)(J ? J : 1) * CB * N, &oom);
+  double *po = out_buf(2, ((size_t)J + 1) * CB, &oom);
+  if (oom) return oom_error(e);
+  vw_status st = VW_OK;
+  for (jsize b0 = 0; b0 < B && st == VW_OK; b0 += CB) {
+    const jsize nb = B - b0 < CB ? B - b0 : CB;
+    if (!gather_rows(e, approx, b0, nb, N, pa)) { st = VW_ERR_ARG; break; }
+    for (jsize l = 0; l < J && st == VW_OK; ++l) {
+      jobjectArray pl = plane(e, details, l);
+      if (!gather_rows(e, pl, b0, nb, N, pd + (size_t)l * nb * N)) st = VW_ERR_ARG;
+      (*e)->DeleteLocalRef(e, pl);
+    }
+    if (st != VW_OK) break;
+    st = vw_energy_planes_f64(CTX(ctx), J ? pd : NULL, pa, nb, N, J, (unsigned)flags | HOST_FLAGS, po);
+    for (jsize k = 0; k <= J && st == VW_OK; ++k)
+      (*e)->SetDoubleArrayRegion(e, out, k * B + b0, nb, po + (size_t)k * nb);
+  }
+  trim_slots();
+  return st;
+}
+
 /* lo == NULL: vw_fin_sharpe_f64; else vw_fin_wavelet_sharpe_f64 */
 static jint fin_sharpe_rows(JNIEnv *e, jlong ctx, jobjectArray returns, const Taps *tl, const Taps *th, jint boundary,
                             jdouble riskFree, jint flags, jdoubleArray out) {

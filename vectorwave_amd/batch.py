@@ -14,7 +14,7 @@ import numpy as np
 from . import _native as nat
 from .engine import Engine, _check, _is_device_tensor
 from .errors import InvalidArgumentException
-from .modwt import BoundaryMode, _check_boundary, _engine_for
+from .modwt import BoundaryMode, _check_boundary, _engine_for, relative_energy
 from .wavelets import Haar, Wavelet
 
 try:
@@ -91,6 +91,27 @@ class BatchMODWT:
                                           wavelet.wavelet_id, nat.PERIODIC, levels,
                                           nat.FLAG_REF_NONFINITE | (nat.FLAG_FMA if fma else 0))
         return MultiLevelResult(det, app)
+
+    @staticmethod
+    def energyBatch(wavelet: Wavelet, signals, levels: int, fma: bool = False, tree_sums: bool = False):
+        """Energy per level of multiLevelAoS(wavelet, signals, levels), without the coefficients: [levels+1, B] in
+        [approx, d1..dJ] order (batch semantics: no level cap, no finite check).  Default: sequential sums, bit
+        for bit the reference's ``energy += c * c`` over multiLevelAoS's arrays; ``tree_sums``: tree reductions,
+        fused with the forward where its cascade fits."""
+        if levels < 1:
+            raise InvalidArgumentException("levels must be >= 1")
+        x = _validate_aos(signals)
+        _check_batch_reach(wavelet, x.shape[1], levels)
+        flags = nat.FLAG_REF_NONFINITE | (nat.FLAG_FMA if fma else 0)
+        if tree_sums:  # the non-finite fix-up belongs to the exact path; tree sums run fused
+            flags = (nat.FLAG_FMA if fma else 0) | nat.FLAG_TREE_SUMS
+        return _engine_for(x).energy(x, wavelet.lowPassDecomposition(), wavelet.highPassDecomposition(),
+                                     wavelet.wavelet_id, nat.PERIODIC, levels, flags)
+
+    @staticmethod
+    def relativeEnergyBatch(wavelet: Wavelet, signals, levels: int, fma: bool = False, tree_sums: bool = False):
+        """getRelativeEnergyDistribution of every signal: [levels+1, B], rows [approx, d1..dJ] / total."""
+        return relative_energy(BatchMODWT.energyBatch(wavelet, signals, levels, fma, tree_sums))
 
     @staticmethod
     def inverseSingleLevelAoS(wavelet: Wavelet, approx, detail, fma: bool = False):

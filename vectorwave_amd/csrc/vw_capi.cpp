@@ -1681,6 +1681,125 @@ extern "C" vw_status vw_fin_wavelet_sharpe_f64(vw_ctx* c, const double* returns,
 }
 
 // ------------------------------------------------------------------------------------------------
+// Wavelet energy per level (vw_energy.hip): MultiLevelMODWTResultImpl.getApproximationEnergy /
+// getDetailEnergyAtLevel (:91-117, computeEnergy :211-216) per signal, out [J+1][B].
+// Timing families: "energy_fused" (k_energy_fused), "energy_chain" (sequential plane sums), "energy_tree".
+
+static vw_status ensure_ws2(vw_ctx* c, size_t bytes) {
+  if (bytes <= c->ws2_bytes) return VW_OK;
+  if (c->capturing) return fail(VW_ERR_STATE, "workspace growth during capture: run the call once before capturing it");
+  if (c->ws2) {
+    hipDeviceSynchronize();
+    ++c->ws_gen;
+    hipFree(c->ws2);
+    c->ws2 = nullptr;
+    c->ws2_bytes = 0;
+  }
+  VW_HIP(hipMalloc(&c->ws2, bytes));
+  c->ws2_bytes = bytes;
+  return VW_OK;
+}
+
+// device pointers in, device pointer out
+static vw_status energy_planes_device(vw_ctx* c, const double* details, const double* approx, int64_t B, int64_t N,
+                                      int J, unsigned flags, double* out) {
+  EnergyPlanesArgs a{};
+  a.approx = approx; a.details = details; a.B = B; a.N = (int)N; a.J = J; a.out = out;
+  a.vec_io = (N % 2 == 0) && ((uintptr_t)approx & 15u) == 0 && ((uintptr_t)details & 15u) == 0;
+  const bool tree = flags & VW_FLAG_TREE_SUMS;
+  LaunchTimer lt(c, tree ? "energy_tree" : "energy_chain");
+  hipError_t e = launch_energy_planes(a, tree, c->cus, c->stream);
+  if (e != hipSuccess) return fail(VW_ERR_DEVICE, "energy launch failed: %s", hipGetErrorString(e));
+  return VW_OK;
+}
+
+// device pointers in, device pointer out; arguments checked by the caller
+static vw_status energy_device(vw_ctx* c, const double* x, int64_t B, int64_t N, int64_t ldx, const double* lo,
+                               const double* hi, int L, int boundary, int J, unsigned flags, double* out) {
+  VW_TRY(capture_guard(c, flags));
+  FwdCall<double> fk;
+  fk.x = x; fk.B = B; fk.N = N; fk.ldx = ldx; fk.lo = lo; fk.hi = hi; fk.L = L; fk.boundary = boundary; fk.J = J;
+  fk.flags = flags; fk.cus = c->cus;
+  EnergyPlan p;
+  plan_energy(c->tune, fk, &p);
+  if (p.fused) {
+    EnergyArgs a = p.args;
+    a.x = x; a.out = out;
+    copy_taps(a.lo, lo, L);
+    copy_taps(a.hi, hi, L);
+    LaunchTimer lt(c, "energy_fused");
+    hipError_t e = launch_energy_fused(a, p.threads, p.lds, p.fma, p.nv, p.grid, c->stream);
+    if (e != hipSuccess) return fail(VW_ERR_DEVICE, "energy launch failed: %s", hipGetErrorString(e));
+  } else {
+    // the forward's own plan and executor into the workspace (approx [B][N] | details [J][B][N]), then the plane sums
+    const size_t plane = (size_t)B * (size_t)N;
+    VW_TRY(ensure_ws2(c, ((size_t)J + 1) * plane * sizeof(double)));
+    double* app = reinterpret_cast<double*>(c->ws2);
+    double* det = app + plane;
+    fk.flags = flags & ~(unsigned)VW_FLAG_SYNC; fk.details = det; fk.approx = app;
+    VW_TRY(forward_impl<double>(c, fk));
+    VW_TRY(energy_planes_device(c, det, app, B, N, J, flags, out));
+  }
+  if (flags & VW_FLAG_SYNC) VW_HIP(hipStreamSynchronize(c->stream));
+  return VW_OK;
+}
+
+extern "C" vw_status vw_modwt_energy_f64(vw_ctx* c, const double* x, int64_t B, int64_t N, int64_t ldx,
+                                         const double* lo, const double* hi, int L, int wid, int boundary, int J,
+                                         unsigned flags, double* out) {
+  (void)wid;
+  // vw_modwt_forward_f64's checks, in its order
+  VW_TRY(check_common(c, x, out, lo, hi, B, N, L, boundary));
+  if (ldx < N) return fail(VW_ERR_ARG, "ldx (%lld) < N (%lld)", (long long)ldx, (long long)N);
+  VW_TRY(check_levels(N, L, J, flags));
+  std::lock_guard<std::recursive_mutex> g(c->mu);
+  hipSetDevice(c->device);
+  if (flags & VW_FLAG_HOST_MEMORY) {
+    if (c->capturing) return fail(VW_ERR_STATE, "host-memory calls cannot be captured (they synchronize)");
+    Staging s(c);
+    double *dx, *dout;
+    VW_TRY(s.in(x, (size_t)(B - 1) * ldx + N, &dx));  // (the last row's padding need not exist)
+    VW_TRY(s.in<double>(nullptr, ((size_t)J + 1) * B, &dout));
+    VW_TRY(energy_device(c, dx, B, N, ldx, lo, hi, L, boundary, J, flags & ~(VW_FLAG_SYNC | VW_FLAG_HOST_MEMORY), dout));
+    VW_TRY(s.out(out, dout, ((size_t)J + 1) * B));
+    VW_HIP(hipStreamSynchronize(c->stream));
+    return ok();
+  }
+  VW_TRY(energy_device(c, x, B, N, ldx, lo, hi, L, boundary, J, flags, out));
+  return ok();
+}
+
+extern "C" vw_status vw_energy_planes_f64(vw_ctx* c, const double* details, const double* approx, int64_t B,
+                                          int64_t N, int J, unsigned flags, double* out) {
+  if (!c) return fail(VW_ERR_NULL, "ctx is null");
+  if (!approx || !out || (!details && J > 0)) return fail(VW_ERR_NULL, "null array argument");
+  if (B <= 0) return fail(VW_ERR_EMPTY, "batch must be non-empty (B=%lld)", (long long)B);
+  if (N <= 0) return fail(VW_ERR_EMPTY, "Signal cannot be empty");
+  if (N > (1LL << 30)) return fail(VW_ERR_ARG, "signal length %lld too large", (long long)N);
+  if (J < 0 || J > kMaxLevels) return fail(VW_ERR_LEVEL, "levels must be in 0..%d", kMaxLevels);
+  if (flags & ~(unsigned)(VW_FLAG_TREE_SUMS | VW_FLAG_HOST_MEMORY | VW_FLAG_SYNC))
+    return fail(VW_ERR_ARG, "vw_energy_planes_f64 takes TREE_SUMS, HOST_MEMORY and SYNC only");
+  std::lock_guard<std::recursive_mutex> g(c->mu);
+  hipSetDevice(c->device);
+  VW_TRY(capture_guard(c, flags));
+  const size_t plane = (size_t)B * (size_t)N;
+  if (flags & VW_FLAG_HOST_MEMORY) {
+    Staging s(c);
+    double *da, *dd = nullptr, *dout;
+    VW_TRY(s.in(approx, plane, &da));
+    if (J > 0) VW_TRY(s.in(details, (size_t)J * plane, &dd));
+    VW_TRY(s.in<double>(nullptr, ((size_t)J + 1) * B, &dout));
+    VW_TRY(energy_planes_device(c, dd, da, B, N, J, flags, dout));
+    VW_TRY(s.out(out, dout, ((size_t)J + 1) * B));
+    VW_HIP(hipStreamSynchronize(c->stream));
+    return ok();
+  }
+  VW_TRY(energy_planes_device(c, details, approx, B, N, J, flags, out));
+  if (flags & VW_FLAG_SYNC) VW_HIP(hipStreamSynchronize(c->stream));
+  return ok();
+}
+
+// ------------------------------------------------------------------------------------------------
 // SWT denoise: fused forward -> per-signal exact median of |d_1| -> inverse with fused threshold.
 extern "C" vw_status vw_noise_sigma_f64(vw_ctx* c, const double* coeffs, int64_t B, int64_t N, unsigned flags,
                                         double* sigma) {

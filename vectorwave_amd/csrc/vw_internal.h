@@ -264,6 +264,46 @@ struct FinArgs {
 hipError_t launch_fin_analyze(const FinArgs& a, hipStream_t st);
 hipError_t launch_fin_sharpe(const FinArgs& a, hipStream_t st);
 
+// Wavelet energy per level (vw_energy.hip): out[0][b] = sum a_J[b][t]^2, out[j][b] = sum d_j[b][t]^2, fp64.
+constexpr int kEnergyWaves = kMaxThreads / 64;
+constexpr int kEnergyRed = (kMaxLevels + 1) * kEnergyWaves;  // LDS doubles behind the level buffers: one partial
+                                                             // per (plane, wave)
+constexpr int kEnergyUnrollMax = 8;  // longest filter with a tap-unrolled k_energy_fused (vw_energy.hip launch_energy_fused)
+// Fused energy forward (k_energy_fused): k_forward_fused's cascade with the stores replaced by sums of squares.
+struct EnergyArgs {
+  const double* x;      // [B][ldx]
+  long long ldx;
+  double* out;          // [J+1][B]
+  long long B;
+  int N;
+  int J;
+  int npow2;
+  int hlpad;            // LDS offset of element 0 (as FwdArgs)
+  int region1;          // element offset of the second level buffer (0 = single buffer)
+  int red_off;          // element offset of the [J+1][kEnergyWaves] wave partials
+  int vec_io;
+  int unrolled;
+  int level_ct;
+  int taps;
+  double lo[kMaxTaps];  // base taps * 1/sqrt(2)
+  double hi[kMaxTaps];
+  LevelDesc lv[kMaxLevels];
+};
+// Energies of coefficient planes already in memory: approx [B][N], details [J][B][N] (nullptr when J = 0).
+struct EnergyPlanesArgs {
+  const double* approx;
+  const double* details;
+  long long B;
+  int N;
+  int J;
+  int vec_io;           // 1: N even and both arrays 16-byte aligned (every row then is)
+  double* out;          // [J+1][B]
+};
+hipError_t launch_energy_fused(const EnergyArgs& a, int threads, int lds_bytes, bool fma, int nv, int grid,
+                               hipStream_t st);
+// tree = false: the reference's sequential sum per row (one lane per row); true: a workgroup tree per row
+hipError_t launch_energy_planes(const EnergyPlanesArgs& a, bool tree, int cus, hipStream_t st);
+
 // Raise a kernel's dynamic-LDS limit past the 64 KiB default once per kernel instantiation AND
 // device (the attribute belongs to the device's copy of the function; a call per launch costs host
 // time).  `once` is a static of the caller, unique per kernel instantiation; several host threads

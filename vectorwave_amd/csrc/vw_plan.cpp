@@ -58,6 +58,7 @@ static const TuningKey kTuningTable[] = {
     VW_KEY("VW_MFMA", t.mfma = v < 0 ? d.mfma : v),
     VW_KEY("VW_REF_GRID", t.ref_grid = v < 0 ? d.ref_grid : v),
     VW_KEY("VW_LEVEL_CT", t.level_ct = v < 0 ? d.level_ct : v != 0),
+    VW_KEY("VW_ENERGY_FUSED", t.energy_fused = v < 0 ? d.energy_fused : v),
 };
 #undef VW_KEY
 
@@ -671,6 +672,58 @@ void plan_forward(const Tuning& tu, const FwdCall<T>& c, FwdPlan<T>* p) {
   p->fused = plan_forward_fused(tu, c, max_hl, p);
   if (!p->fused) plan_forward_levels(tu, c, p);
   reserve_ref<T>(tu, c.cus, c.B, c.N, p);
+}
+
+// ------------------------------------------------------------------------------------------------
+// Energy per level (vw_energy.hip).  The fused kernel is the VW_FLAG_TREE_SUMS path: it runs where the plain
+// fused forward would -- the cascade fits LDS and 1024 threads x NV, any L and boundary -- but not for the
+// calls whose forward does more than the cascade (validation, the FFT-switch levels, the REF_NONFINITE
+// fix-up): those, and the default sequential sums, go through the forward's own plan and the plane sums.
+// Level buffers, after the forward's measurements on the same cascade (plan_forward_fused): the EXACT arithmetic
+// runs with one buffer (half the LDS, twice the workgroups to overlap its longer chains), FMA with two (one
+// barrier per level) while two workgroups still fit a CU.  Whole waves
+// (the kernel folds partials with wave butterflies); kEnergyRed doubles of wave partials follow the buffers.
+void plan_energy(const Tuning& tu, const FwdCall<double>& c, EnergyPlan* p) {
+  constexpr int V = vec_width<double>();
+  const int64_t N = c.N, nvec = (N + V - 1) / V;
+  const int L = c.L, J = c.J;
+  EnergyArgs& a = p->args;
+  p->fma = c.flags & VW_FLAG_FMA;
+  p->fused = false;
+  if (!(c.flags & VW_FLAG_TREE_SUMS) || tu.energy_fused == 0 || tu.force_tiled || J < 1 || J > kMaxLevels ||
+      (c.flags & (VW_FLAG_VALIDATE | VW_FLAG_REF_NONFINITE)) || c.hist || c.single_level)
+    return;
+  const int max_hl = forward_levels(c, a.lv);
+  for (int j = 0; j < J; ++j)
+    if (a.lv[j].mode == kHaloFftPad) return;
+  const int hlpad = (int)round_up(max_hl, V);
+  const int64_t region = round_up(hlpad + nvec * V + V, V);
+  int threads = 0, lds = 0, nv = 4;
+  bool fit = false;
+  bool dbl = p->fma && (2 * region + kEnergyRed) * (int64_t)sizeof(double) <= kLdsBytes / 2 &&
+             fused_plan(tu, N, V, sizeof(double), 2 * region + kEnergyRed, &threads, &nv, &lds, &fit);
+  if (!dbl && !fused_plan(tu, N, V, sizeof(double), region + kEnergyRed, &threads, &nv, &lds, &fit)) return;
+  threads = (int)round_up(threads, 64);  // <= 512 (NV = 4) / 1024 (NV = 8): fused_plan's bounds are multiples of 64
+  fit = (int64_t)(nv - 1) * threads <= nvec;
+  const bool io_aligned = (c.ldx % V == 0) && (N % V == 0) && aligned16(c.x);
+  a.B = c.B; a.N = (int)N; a.J = J; a.ldx = c.ldx;
+  a.npow2 = next_pow2(N);
+  a.taps = L;
+  for (int j = 0; j < J; ++j) set_halo_images(a.lv[j], N, a.npow2, V, threads, nv);
+  a.hlpad = hlpad;
+  a.region1 = dbl ? (int)region : 0;
+  a.red_off = (int)((dbl ? 2 : 1) * region);
+  a.vec_io = io_aligned;
+  a.unrolled = io_aligned && fit && L <= tu.unroll_max && L <= kEnergyUnrollMax && has_unrolled_taps(L);
+  a.level_ct = tu.level_ct;
+  // a few workgroups per CU, grid-stride over the rows: what LDS and the kernels' wave bounds
+  // (k_energy_fused: 6 waves per SIMD for NV = 4 and L <= 8, else 4) let be resident at once
+  const int wpe = (nv <= 4 && L <= 8) ? 6 : 4;
+  const int by_waves = std::max(1, wpe * 4 / (threads / 64));
+  const int by_lds = std::max(1, kLdsBytes / std::max(lds, 1));
+  p->grid = (int)std::min<int64_t>(c.B, (int64_t)std::max(c.cus, 1) * std::min(by_waves, by_lds));
+  p->threads = threads; p->nv = nv; p->lds = lds;
+  p->fused = true;
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -61,6 +61,8 @@ struct Tuning {
                                // short filters (L <= 8), as before (profiles/r07/ab_db4_level_ct.log)
   int mfma = 0;                // VW_MFMA=1|2|3: fp32 FMA PERIODIC forward (1) / inverse (2) / both (3) on the matrix
                                // cores (vw_mfma.hip)
+  int energy_fused = 1;        // VW_ENERGY_FUSED=0: vw_modwt_energy_f64 never runs the fused energy kernel (forward
+                               // into the workspace, then the plane sums), also under VW_FLAG_TREE_SUMS
 };
 
 // One switch of the Tuning struct by its environment name; value < 0 = the default.  Returns false
@@ -167,6 +169,17 @@ struct Plan {
 };
 template <typename T> using FwdPlan = Plan<T, FwdArgs<T>>;
 template <typename T> using InvPlan = Plan<T, InvArgs<T>>;
+
+// vw_modwt_energy_f64 (vw_energy.hip): whether the fused energy kernel runs and with what launch shape.  Not
+// fused: the executor runs plan_forward's plan into its workspace and sums the planes there.
+struct EnergyPlan {
+  bool fused = false;
+  bool fma = false;
+  int threads = 0, nv = 4, lds = 0;
+  int grid = 0;          // workgroups (grid-stride over the rows)
+  EnergyArgs args{};     // every non-pointer field
+};
+void plan_energy(const Tuning& tu, const FwdCall<double>& c, EnergyPlan* p);
 
 // `p` must be a freshly constructed plan.
 template <typename T> void plan_forward(const Tuning& tu, const FwdCall<T>& c, FwdPlan<T>* p);

@@ -288,6 +288,36 @@ class Engine:
                                                   self._flags(flags, dev), self._ptr(out, dev)))
         return out
 
+    # -- wavelet energy per level (vw_modwt_energy_f64 / vw_energy_planes_f64) ---------------------
+    def energy(self, x, lo: Sequence[float], hi: Sequence[float], wavelet_id: int, boundary: int, levels: int,
+               flags: int = 0, N: Optional[int] = None):
+        """Energies of the multi-level forward of x [N] or [B,N] -> [J+1, B]: row 0 the approximation energy, row j
+        the detail energy of level j.  Default: the reference's sequential ``energy += c * c`` bit for bit;
+        FLAG_TREE_SUMS: tree sums, fused with the forward where its cascade fits (no coefficient leaves the GPU's
+        LDS).  ``N``: row length when the array is wider (its width is the leading dimension)."""
+        xa, dev, xp, B, n, ld = self._rows(x, N)
+        out = self._empty(xa, dev, (levels + 1, B))
+        _check(self.lib.vw_modwt_energy_f64(self.ctx, xp, B, n, ld, nat.taps_array(lo), nat.taps_array(hi), len(lo),
+                                            wavelet_id, boundary, levels, self._flags(flags, dev),
+                                            self._ptr(out, dev)))
+        return out
+
+    def energy_planes(self, details, approx, flags: int = 0):
+        """Energies of coefficient planes: details [J,B,N] (or [J,N]; None = no levels), approx [B,N] (or [N])
+        -> [J+1, B] in [approx, d1..dJ] order."""
+        aa, dev, ap, _ = self._prep(approx, np.float64)
+        B, N = (1, aa.shape[0]) if aa.ndim == 1 else aa.shape
+        J, dp = 0, None
+        if details is not None and details.shape[0] > 0:
+            da, ddev, dp, _ = self._prep(details, np.float64)
+            J = int(da.shape[0])
+            if ddev != dev or tuple(da.shape[1:]) != tuple(aa.shape):
+                raise ValueError("details must be [J] + approx.shape, in the same memory as approx")
+        out = self._empty(aa, dev, (J + 1, B))
+        _check(self.lib.vw_energy_planes_f64(self.ctx, dp, ap, B, N, J, self._flags(flags, dev),
+                                             self._ptr(out, dev)))
+        return out
+
     def transpose(self, a, rows: int, cols: int):
         """out[c][r] = a[r][c] (a: rows*cols elements, any shape) -> flat [cols*rows] array."""
         aa, dev, ap, f32 = self._prep(a)

@@ -69,6 +69,22 @@ def _length(x) -> int:
     return int(x.shape[-1])
 
 
+def relative_energy(energies):
+    """getRelativeEnergyDistribution (MultiLevelMODWTResultImpl.java:121-138) per signal, from energies [J+1, B] in
+    [approx, d1..dJ] order: ``total = approx; total += d_1 ... d_J`` in that order, then every energy / total; a
+    signal whose total is 0.0 gets zeros.  Elementwise numpy / torch operations in the reference's order: the
+    values are the reference's bit for bit.  Returns [J+1, B] in the same memory as the input."""
+    total = energies[0].clone() if _is_device_tensor(energies) else np.array(energies[0], dtype=np.float64, copy=True)
+    for j in range(1, energies.shape[0]):
+        total = total + energies[j]
+    zero = total == 0.0
+    if _is_device_tensor(energies):
+        safe = torch.where(zero, torch.ones_like(total), total)
+        return torch.where(zero.unsqueeze(0), torch.zeros_like(energies), energies / safe.unsqueeze(0))
+    safe = np.where(zero, 1.0, total)
+    return np.where(zero[None, :], 0.0, np.asarray(energies, dtype=np.float64) / safe[None, :])
+
+
 # ----------------------------------------------------------------------------------------------
 class MODWTResult:
     """core/modwt/MODWTResult.java:36-100 -- getters return defensive copies."""
@@ -135,6 +151,22 @@ class MultiLevelMODWTResult:
         if tot == 0:
             return [0.0] * (J + 1)
         return [self.getApproximationEnergy() / tot] + [self.getDetailEnergyAtLevel(j) / tot for j in range(1, J + 1)]
+
+    def energiesPerSignal(self, tree_sums: bool = False):
+        """Energies per signal of a (batched) result: [J+1, B] in [approx, d1..dJ] order (B = 1 for a single
+        signal).  Device tensors are summed on the device (Engine.energy_planes; ``tree_sums``: tree reductions
+        instead of the reference's sequential order); host arrays with the sequential ``np.add.accumulate``."""
+        if _is_device_tensor(self._app):
+            eng = Engine.get(self._app.device.index)
+            return eng.energy_planes(self._det, self._app, nat.FLAG_TREE_SUMS if tree_sums else 0)
+        app = np.asarray(self._app, dtype=np.float64)
+        det = np.asarray(self._det, dtype=np.float64)
+        if app.ndim == 1:
+            app, det = app[None, :], det[:, None, :]
+        planes = np.concatenate([app[None], det], axis=0)
+        if planes.shape[-1] == 0:
+            return np.zeros(planes.shape[:2])
+        return np.add.accumulate(planes * planes, axis=-1)[..., -1]
 
     def isValid(self) -> bool:
         if _is_device_tensor(self._app):
@@ -330,6 +362,24 @@ class MultiLevelMODWTTransform:
         """decomposeMutable :267-330."""
         det, app = self._decompose_arrays(signal, levels)
         return MutableMultiLevelMODWTResult(det, app)
+
+    def energyBatch(self, signals, levels: Optional[int] = None, tree_sums: bool = False):
+        """Energy per level of decompose(signals, levels), without the coefficients: [J+1, B] in
+        getRelativeEnergyDistribution's [approx, d1..dJ] order (signals [B, N], or [N] with B = 1).  Default: the
+        reference's decompose + computeEnergy bit for bit (sequential sums); ``tree_sums``: tree reductions,
+        fused with the forward where its cascade fits."""
+        _validate_signal(signals)
+        if levels is None:
+            levels = self.getMaximumLevels(_length(signals))
+        w = self.wavelet
+        flags = (nat.FLAG_CORE_LEVELS | nat.FLAG_VALIDATE | nat.FLAG_FFT_SWITCH | self._fma |
+                 (nat.FLAG_TREE_SUMS if tree_sums else 0))
+        return _engine_for(signals).energy(signals, w.lowPassDecomposition(), w.highPassDecomposition(), w.wavelet_id,
+                                           int(self.boundaryMode), levels, flags)
+
+    def relativeEnergyBatch(self, signals, levels: Optional[int] = None, tree_sums: bool = False):
+        """getRelativeEnergyDistribution of every signal: [J+1, B], rows [approx, d1..dJ] / total."""
+        return relative_energy(self.energyBatch(signals, levels, tree_sums))
 
     def _reconstruct(self, result: MultiLevelMODWTResult, mask: int, approx_zero: bool, guard: bool = True):
         if result is None:
