@@ -1,6 +1,6 @@
 // TEST INFRASTRUCTURE: walks a matrix of calls and tunings through the planner (vectorwave_amd/csrc/vw_plan.cpp,
 // linked without anything from HIP) and checks every plan against the kernels' launch contracts, then compares
-// the pinned configurations.  Prints nothing when all is well; otherwise one line per finding: the call, the
+// the pinned configurations and the padded-layout rule (blk_pad) with its table of values.  Prints nothing when all is well; otherwise one line per finding: the call, the
 // plan as text and the broken rule.  tests/test_plan_cpu.py fails on any output.
 //   plan_check                      the whole matrix and the pins
 //   plan_check show fwd|inv f64|f32 B N L J boundary flags [wid] [VW_KEY=value ...]     one plan as text
@@ -448,6 +448,37 @@ static void run_pins() {
   }
 }
 
+// ------------------------------------------------------------------------------------------------
+// The padded layout of the register-blocked kernels (blk_pad, vw_internal.h): the planner sizes LDS with it and
+// the kernels address LDS with it.  Literal values, not computed by the rule: vector stride m, outputs per
+// thread nv, tight -> (shift, pad).
+struct PadPin {
+  int m, nv, tight, sh, pad;
+};
+static const PadPin kPadPins[] = {
+    {0, 4, 0, 30, 0},   {0, 4, 1, 30, 0},   {0, 8, 0, 30, 0},   {0, 8, 1, 30, 0},    //
+    {1, 4, 0, 2, 1},    {1, 4, 1, 2, 1},    {1, 8, 0, 3, 1},    {1, 8, 1, 4, 1},     //
+    {2, 4, 0, 2, 1},    {2, 4, 1, 2, 1},    {2, 8, 0, 3, 1},    {2, 8, 1, 4, 1},     //
+    {4, 4, 0, 2, 1},    {4, 4, 1, 2, 1},    {4, 8, 0, 3, 1},    {4, 8, 1, 4, 1},     //
+    {8, 4, 0, 3, 2},    {8, 4, 1, 3, 2},    {8, 8, 0, 3, 1},    {8, 8, 1, 4, 1},     //
+    {16, 4, 0, 30, 0},  {16, 4, 1, 30, 0},  {16, 8, 0, 30, 0},  {16, 8, 1, 30, 0},   //
+    {32, 4, 0, 30, 0},  {32, 4, 1, 30, 0},  {32, 8, 0, 30, 0},  {32, 8, 1, 30, 0},   //
+    {64, 4, 0, 30, 0},  {64, 4, 1, 30, 0},  {64, 8, 0, 30, 0},  {64, 8, 1, 30, 0},   //
+    {128, 4, 0, 30, 0}, {128, 4, 1, 30, 0}, {128, 8, 0, 30, 0}, {128, 8, 1, 30, 0},  //
+};
+static_assert(blk_pad(8, 4).sh == 3 && blk_pad(8, 4).pad == 2, "blk_pad is usable in constant expressions (BlkC)");
+
+static void run_pad_pins() {
+  for (const PadPin& pin : kPadPins) {
+    const BlkLayout got = blk_pad(pin.m, pin.nv, pin.tight);
+    if (got.sh != pin.sh || got.pad != pin.pad) {
+      ++g_findings;
+      printf("blk_pad(m=%d, nv=%d, tight=%d): expected (%d, %d), got (%d, %d)\n", pin.m, pin.nv, pin.tight, pin.sh,
+             pin.pad, got.sh, got.pad);
+    }
+  }
+}
+
 template <typename T>
 static int show(bool inverse, char** v, int n) {
   if (n < 6) return 2;
@@ -488,6 +519,7 @@ int main(int argc, char** argv) {
   run_matrix<double>();
   run_matrix<float>();
   run_pins();
+  run_pad_pins();
   if (g_findings > 200) printf("... %d findings in all\n", g_findings);
   return g_findings ? 1 : 0;
 }

@@ -156,7 +156,7 @@ def test_swt_denoise_nonperiodic_nonfinite(engine, boundary, soft):
 
 
 def test_config3_kernels_flag_their_own_rows(engine):
-    # config 3 runs the register-blocked kernels (k_forward_blk / k_inverse_blk), which probe their details /
+    # config 3 runs the register-blocked kernels (vw_blk.h k_forward_blk / k_inverse_blk), which probe their details /
     # output in-line: no scan of the call's planes (timing family "ref_nonfinite", not "..._scan")
     w, n, J = Symlet.SYM8, 16384, 8
     x = poisoned(3, n, 7)

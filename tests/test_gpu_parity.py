@@ -689,7 +689,7 @@ def test_forward_strided_rows_ldx(engine):
         assert torch.equal(det, d2) and torch.equal(app, a2)
 
 
-# ---- register-blocked PERIODIC kernels (long filters, vw_device.h k_forward_blk / k_inverse_blk) --------
+# ---- register-blocked PERIODIC kernels (long filters, vw_blk.h k_forward_blk / k_inverse_blk) --------
 @pytest.mark.parametrize("case", [("sym8", 16384, 8, "f64", 3), ("sym8", 4096, 8, "f64", 5), ("db8", 4096, 6, "f64", 5),
                                   ("coif5", 8192, 6, "f32", 6), ("coif5", 4096, 5, "f64", 3), ("db6", 2048, 7, "f64", 4)],
                          ids=lambda c: f"{c[0]}-{c[1]}-J{c[2]}-{c[3]}")

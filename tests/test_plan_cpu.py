@@ -7,8 +7,10 @@ Every plan must respect the launch contracts the kernels state (a kernel without
 listed tap count, LDS and thread limits, the persistent and register-blocked kernels' shapes, level coverage
 and buffer ping-pong on the per-level path, probing only by kernels that probe, everything reserved before
 the first launch).  The bench configurations, the 512-row headline shard and the filter lengths outside the
-unrolled list are pinned as exact plans (tests/plan_harness/pins.inc).  The program prints one line per
-finding and nothing otherwise.
+unrolled list are pinned as exact plans (tests/plan_harness/pins.inc).  The padded LDS layout of the
+register-blocked kernels (blk_pad in vw_internal.h, the one rule the planner and the kernels share) is pinned
+as a literal table over vector stride x outputs per thread x tight.  The program prints one line per finding
+and nothing otherwise.
 """
 import os
 import subprocess

@@ -1210,9 +1210,6 @@ __global__ void VW_FUSED_BOUNDS(NV, VW_FUSED_W(L, 6)) k_inverse_db(const InvArgs
 
 // Single-buffer sequential-sum form for signals too long for two LDS buffers: ONE region is
 // time-shared (a_j -> approx branch -> d_j -> detail branch -> a_{j-1}); four barriers per level.
-#ifndef VW_INV_LATE_PF
-#define VW_INV_LATE_PF 0
-#endif
 #ifndef VW_INV_W
 #define VW_INV_W 6  // waves per SIMD of k_inverse_seq (experiment builds: -DVW_INV_W=8 -> 64 VGPRs)
 #endif
@@ -1245,22 +1242,14 @@ __global__ void VW_FUSED_BOUNDS(NV, VW_FUSED_W(L, VW_INV_W)) k_inverse_seq(const
   for (int j = p.J; j >= 1; --j) {
     const LevelDesc lv = p.lv[j - 1];
     lds_barrier();  // R = a_j + halo
-#if VW_INV_LATE_PF
-    // (experiment) d_j issued at the start of level j, live only across the approximation branch
-    if (j < p.J)
-      load_row_regs<T, NV, FULL>(dreg, p.details + (size_t)(j - 1) * plane + b * (size_t)N, N, nvec, vec_ok,
-                           lv.use_d == 0);
-#endif
     zero_regs<T, NV>(acc);
     inv_row<T, L, FMA, NV, FULL>(R, nvec, lv.s, lv.dir_a, lv.off_a, p.lo, p.taps, p.level_ct, acc);
     lds_barrier();  // every approximation-branch read done
     wait_vmem();    // the d_j prefetch
     regs_to_level<T, L, NV, FULL>(R, dreg, nvec, N, lv, 0, (const T*)nullptr, lv.use_d == 0, p.thr, thr_of(j), p.soft);
-#if !VW_INV_LATE_PF
-    if (j > 1)
+    if (j > 1)  // the d_{j-1} prefetch, in flight across the detail branch
       load_row_regs<T, NV, FULL>(dreg, p.details + (size_t)(j - 2) * plane + b * (size_t)N, N, nvec, vec_ok,
                            p.lv[j - 2].use_d == 0);
-#endif
     lds_barrier();  // R = d_j + halo
     inv_row<T, L, FMA, NV, FULL>(R, nvec, lv.s, lv.dir_d, lv.off_d, p.hi, p.taps, p.level_ct, acc);
     if (j > 1) {
@@ -1275,671 +1264,12 @@ __global__ void VW_FUSED_BOUNDS(NV, VW_FUSED_W(L, VW_INV_W)) k_inverse_seq(const
   }
 }
 
-// ---------------------------------------------------------------------------------------------
-// Register-blocked PERIODIC kernels for long filters (L > 8: sym8, coif5, ...).  At a level with
-// spacing s >= V (vector stride m = s/V) a thread owns the NV output vectors vb, vb+m, .., vb+(NV-1)m
-// of a block of m columns; they read the same input vectors shifted by one tap, so a branch costs
-// NV+L-1 LDS reads instead of NV*L (33 vs 120 at L = 30): the per-level LDS read traffic, which bounds
-// the one-vector-per-tap kernels for long filters, drops ~3.6x.  The block mapping alone would put
-// 4..16 lanes of one ds_read_b128 lane group on the same banks, so every level input is written into
-// LDS in a padded layout chosen for that level -- NV = 4: one pad vector per 4 (m <= 4), two per 8
-// (m = 8); NV = 8: one per 8 (m <= 8); none for m >= 16 -- under which the reads are conflict-free
-// (modelled with the gfx950 lane groups of the microarchitecture guide's LDS table).  Levels with
-// s < V run the register-window code in the standard mapping.  Per output the taps run i ascending
-// (forward: ScalarOps.java:707-719; inverse: approximation branch then detail branch,
-// MultiLevelMODWTTransform.java:576-589): the reference's sums bit for bit in EXACT mode.
-struct BlkLayout {
-  int sh, pad;  // logical vector u -> u + (u >> sh) * pad
-};
+}  // namespace vw
 
-// tight (host: the standard layout does not fit LDS, e.g. sym8 at N = 16384): NV = 8 pads one
-// vector per 16 -- 6 % of LDS instead of 12.5 %, 1.3-2x the conflict-free cycles, still 3-4x fewer
-// than the one-vector-per-tap reads.
-__device__ __forceinline__ BlkLayout blk_layout(int m, int nv, int tight = 0) {
-  if (m <= 0 || m >= 16) return BlkLayout{30, 0};
-  if (nv >= 8) return tight ? BlkLayout{4, 1} : BlkLayout{3, 1};
-  if (m == 8) return BlkLayout{3, 2};
-  return BlkLayout{2, 1};
-}
+// the register-blocked PERIODIC kernels for long filters (k_forward_blk / k_inverse_blk, BlkC)
+#include "vw_blk.h"
 
-__device__ __forceinline__ int blk_phys(const BlkLayout& lo, int u) { return u + (u >> lo.sh) * lo.pad; }
-
-template <typename T>
-__device__ __forceinline__ void blk_store(T* R, const BlkLayout& lo, int u, const typename VT<T>::v& o) {
-  *reinterpret_cast<typename VT<T>::v*>(R + blk_phys(lo, u) * VT<T>::V) = o;
-}
-
-// thread tid's block base at vector stride m (NV vectors per column)
-template <int NV>
-__device__ __forceinline__ int blk_base(int m) {
-  const int tid = threadIdx.x;
-  return (tid / m) * (m * NV) + tid % m;
-}
-
-// Tap chunk of the blocked kernels: 8, or 4 where NV = 8 fp64 accumulators already take 32-64 VGPRs
-// (1024-thread workgroups cap a lane at 128 VGPRs; 8-tap chunks spilled there).
-template <typename T, int NV>
-constexpr int blk_chunk() { return (NV >= 8 && sizeof(T) == 8) ? 4 : kWinTaps; }
-
-// One branch of the inverse (reads t + i*s): acc[r] (+)= f[i] * in[vb + (r+i)m], i ascending per r.
-// Taps in chunks of kWinTaps (each re-read at its start): NV+TC-1 reads per chunk, the chunk's taps
-// the only ones live.
-template <typename T, int L, bool FMA, int NV>
-__device__ __forceinline__ void blk_inv_branch(const T* R, const BlkLayout& lo, int vb, int m, const T* f,
-                                               T (&acc)[NV][VT<T>::V]) {
-  constexpr int V = VT<T>::V;
-  using vec = typename VT<T>::v;
-  constexpr int TC = blk_chunk<T, NV>();
-  static_for<0, (L + TC - 1) / TC>([&](auto c) __attribute__((always_inline)) {
-    constexpr int I0 = decltype(c)::value * TC;
-    constexpr int I1 = (I0 + TC < L) ? I0 + TC : L;
-    T fc[I1 - I0];
-#pragma unroll
-    for (int i = I0; i < I1; ++i) fc[i - I0] = f[i];
-#pragma unroll
-    for (int q = I0; q < I1 + NV - 1; ++q) {
-      const vec x = *reinterpret_cast<const vec*>(R + blk_phys(lo, vb + q * m) * V);
-#pragma unroll
-      for (int r = 0; r < NV; ++r) {
-        const int i = q - r;
-        if (i >= I0 && i < I1) {
-          vmadd<FMA>(acc[r], x, fc[i - I0]);
-        }
-      }
-      if (((q - I0) & 3) == 3) __builtin_amdgcn_sched_barrier(0);  // bounded reads in flight
-    }
-  });
-#pragma unroll
-  for (int r = 0; r < NV; ++r)
-#pragma unroll
-    for (int e = 0; e < V; ++e) asm volatile("" : "+v"(acc[r][e]));  // pin the sums (see inv_row_t)
-}
-
-// Compile-time form of blk_layout at vector stride M (NV outputs per column, TIGHT: blk_tight).  A
-// thread's block base vb = (tid/M)*M*NV + tid%M; when M*NV is a multiple of the pad group 2^SH, the
-// physical offset of logical vector vb + q*M from vb's is off(q) for every thread, so the branch
-// reads at immediate offsets from one base address instead of computing u + (u >> SH)*PAD per read.
-template <int M, int NV, int TIGHT>
-struct BlkC {
-  static constexpr int SH = (M >= 16) ? 30 : (NV >= 8 ? (TIGHT ? 4 : 3) : (M == 8 ? 3 : 2));
-  static constexpr int PAD = (M >= 16) ? 0 : (NV >= 8 ? 1 : (M == 8 ? 2 : 1));
-  static constexpr bool ok = PAD == 0 || (M * NV) % (1 << SH) == 0;
-  static constexpr int off(int q) { return q * M + ((q * M) >> SH) * PAD; }
-};
-
-// blk_inv_branch at a compile-time stride: Rb = R + blk_phys(layout, vb) * V
-template <typename T, int L, bool FMA, int NV, int M, int TIGHT>
-__device__ __forceinline__ void blk_inv_branch_c(const T* Rb, const T* f, T (&acc)[NV][VT<T>::V]) {
-  constexpr int V = VT<T>::V;
-  using vec = typename VT<T>::v;
-  using C = BlkC<M, NV, TIGHT>;
-  constexpr int TC = blk_chunk<T, NV>();
-  static_for<0, (L + TC - 1) / TC>([&](auto c) __attribute__((always_inline)) {
-    constexpr int I0 = decltype(c)::value * TC;
-    constexpr int I1 = (I0 + TC < L) ? I0 + TC : L;
-    T fc[I1 - I0];
-#pragma unroll
-    for (int i = I0; i < I1; ++i) fc[i - I0] = f[i];
-#pragma unroll
-    for (int q = I0; q < I1 + NV - 1; ++q) {
-      const vec x = *reinterpret_cast<const vec*>(Rb + C::off(q) * V);
-#pragma unroll
-      for (int r = 0; r < NV; ++r) {
-        const int i = q - r;
-        if (i >= I0 && i < I1) {
-          vmadd<FMA>(acc[r], x, fc[i - I0]);
-        }
-      }
-      if (((q - I0) & 3) == 3) __builtin_amdgcn_sched_barrier(0);
-    }
-  });
-#pragma unroll
-  for (int r = 0; r < NV; ++r)
-#pragma unroll
-    for (int e = 0; e < V; ++e) asm volatile("" : "+v"(acc[r][e]));
-}
-
-// blk_inv_branch with wave-uniform offsets: under the same condition as BlkC::ok (the pad groups
-// align with a thread's block), the physical offset of logical vector vb + q*m from vb's is
-// q*m + ((q*m) >> sh)*pad for every thread -- a scalar value per read, so a read costs one vector
-// add (base + scalar offset) instead of the per-lane shift / multiply / add of blk_phys.  One code
-// copy for every stride (the compile-time forms, one copy per m, measured slower at NV = 8).
-template <typename T, int L, bool FMA, int NV>
-__device__ __forceinline__ void blk_inv_branch_s(const T* Rb, int m, int sh, int pad, const T* f,
-                                                 T (&acc)[NV][VT<T>::V]) {
-  constexpr int V = VT<T>::V;
-  using vec = typename VT<T>::v;
-  constexpr int TC = blk_chunk<T, NV>();
-  static_for<0, (L + TC - 1) / TC>([&](auto c) __attribute__((always_inline)) {
-    constexpr int I0 = decltype(c)::value * TC;
-    constexpr int I1 = (I0 + TC < L) ? I0 + TC : L;
-    T fc[I1 - I0];
-#pragma unroll
-    for (int i = I0; i < I1; ++i) fc[i - I0] = f[i];
-#pragma unroll
-    for (int q = I0; q < I1 + NV - 1; ++q) {
-      const int qm = __builtin_amdgcn_readfirstlane(q * m);
-      const int off = __builtin_amdgcn_readfirstlane(qm + (qm >> sh) * pad);
-      const vec x = *reinterpret_cast<const vec*>(Rb + off * V);
-#pragma unroll
-      for (int r = 0; r < NV; ++r) {
-        const int i = q - r;
-        if (i >= I0 && i < I1) {
-          vmadd<FMA>(acc[r], x, fc[i - I0]);
-        }
-      }
-      if (((q - I0) & 3) == 3) __builtin_amdgcn_sched_barrier(0);
-    }
-  });
-#pragma unroll
-  for (int r = 0; r < NV; ++r)
-#pragma unroll
-    for (int e = 0; e < V; ++e) asm volatile("" : "+v"(acc[r][e]));
-}
-
-#ifndef VW_BLK_SOFF
-#define VW_BLK_SOFF 1  // NV = 8 inverse branch: wave-uniform offsets where the layout allows (0: per-lane blk_phys)
-#endif
-#ifndef VW_BLK_CK8
-#define VW_BLK_CK8 1  // NV = 8 blocked inverse (FMA) at m = 1..64: immediate LDS offsets off one laundered base
-                      // (the same for k_forward_blk measured slower: forward 4.92-4.97 vs 4.78-4.85 ms, sym8)
-#endif
-
-// blk_inv_branch_c with the base laundered into a 32-bit LDS address (lds_base): every read is one
-// ds_read_b128 at an immediate offset -- no per-read scalar offset arithmetic (blk_inv_branch_s: four SALU
-// and one VALU per read) and no re-based 64-bit pointers.
-template <typename T, int L, bool FMA, int NV, int M, int TIGHT>
-__device__ __forceinline__ void blk_inv_branch_cl(const T* Rb, const T* f, T (&acc)[NV][VT<T>::V]) {
-  constexpr int V = VT<T>::V;
-  using vec = typename VT<T>::v;
-  using C = BlkC<M, NV, TIGHT>;
-  constexpr int TC = blk_chunk<T, NV>();
-  const unsigned ab = lds_base(Rb);
-  static_for<0, (L + TC - 1) / TC>([&](auto c) __attribute__((always_inline)) {
-    constexpr int I0 = decltype(c)::value * TC;
-    constexpr int I1 = (I0 + TC < L) ? I0 + TC : L;
-    T fc[I1 - I0];
-#pragma unroll
-    for (int i = I0; i < I1; ++i) fc[i - I0] = f[i];
-#pragma unroll
-    for (int q = I0; q < I1 + NV - 1; ++q) {
-      const vec x = lds_vec_at<vec>(ab + (unsigned)(C::off(q) * V * (int)sizeof(T)));
-#pragma unroll
-      for (int r = 0; r < NV; ++r) {
-        const int i = q - r;
-        if (i >= I0 && i < I1) {
-          vmadd<FMA>(acc[r], x, fc[i - I0]);
-        }
-      }
-      if (((q - I0) & 3) == 3) __builtin_amdgcn_sched_barrier(0);
-    }
-  });
-#pragma unroll
-  for (int r = 0; r < NV; ++r)
-#pragma unroll
-    for (int e = 0; e < V; ++e) asm volatile("" : "+v"(acc[r][e]));
-}
-
-// One inverse branch at vector stride m >= 1: the compile-time forms for m = 1..64 (immediate LDS
-// offsets stay below 64 KiB for L <= 30), the generic one otherwise.  Same reads, same sums.
-template <typename T, int L, bool FMA, int NV>
-__device__ __forceinline__ void blk_inv_any(const T* R, const BlkLayout& lo, int tight, int vb, int m, const T* f,
-                                            T (&acc)[NV][VT<T>::V]) {
-  constexpr int V = VT<T>::V;
-  if constexpr (NV >= 8) {
-    // compile-time forms through plain pointers measured slower at NV = 8 (sym8 fp64 inverse 7.18 -> 8.08 ms,
-    // profiles/r03/ab_sym8_cinv.log); off a laundered 32-bit base (blk_inv_branch_cl) they win: 6.32-6.38
-    // -> 6.17-6.28 ms (profiles/r05/ab_sym8_inverse_ck8.log)
-    const int sh = __builtin_amdgcn_readfirstlane(lo.sh), pad = __builtin_amdgcn_readfirstlane(lo.pad);
-    if constexpr (VW_BLK_CK8 != 0 && FMA) {
-      // m = 1..64 where the pad group (8 vectors, or 16 in the tight layout) divides a thread's 8m-vector
-      // block (BlkC::ok) or there is none (m >= 16): the offset of vb + q*m from vb is the same for every
-      // lane.  FMA only: the EXACT kernel (mul + add per tap) spills 28 B/lane at its 128-VGPR cap with it.
-      const T* Rb = R + blk_phys(lo, vb) * V;
-      const int sel = (m == 1 || m == 2 || m == 4 || m == 8) && pad == 1 ? m * 2 + (tight ? 1 : 0)
-                      : (m == 16 || m == 32 || m == 64) && pad == 0 ? 4 * m : 0;
-      switch (sel) {
-        case 2: blk_inv_branch_cl<T, L, FMA, NV, 1, 0>(Rb, f, acc); return;
-        // (m = 1 in the tight layout: a thread's 8-vector block is half a 16-vector pad group -- per lane)
-        case 4: blk_inv_branch_cl<T, L, FMA, NV, 2, 0>(Rb, f, acc); return;
-        case 5: blk_inv_branch_cl<T, L, FMA, NV, 2, 1>(Rb, f, acc); return;
-        case 8: blk_inv_branch_cl<T, L, FMA, NV, 4, 0>(Rb, f, acc); return;
-        case 9: blk_inv_branch_cl<T, L, FMA, NV, 4, 1>(Rb, f, acc); return;
-        case 16: blk_inv_branch_cl<T, L, FMA, NV, 8, 0>(Rb, f, acc); return;
-        case 17: blk_inv_branch_cl<T, L, FMA, NV, 8, 1>(Rb, f, acc); return;
-        case 64: blk_inv_branch_cl<T, L, FMA, NV, 16, 0>(Rb, f, acc); return;   // m >= 16: natural layout
-        case 128: blk_inv_branch_cl<T, L, FMA, NV, 32, 0>(Rb, f, acc); return;
-        case 256: blk_inv_branch_cl<T, L, FMA, NV, 64, 0>(Rb, f, acc); return;
-        default: break;
-      }
-    }
-    if (VW_BLK_SOFF && (pad == 0 || ((m * NV) & ((1 << sh) - 1)) == 0))
-      blk_inv_branch_s<T, L, FMA, NV>(R + blk_phys(lo, vb) * V, m, sh, pad, f, acc);
-    else
-      blk_inv_branch<T, L, FMA, NV>(R, lo, vb, m, f, acc);
-  } else {
-    const T* Rb = R + blk_phys(lo, vb) * V;
-    auto go = [&](auto mc, auto tc) __attribute__((always_inline)) {
-      constexpr int M = decltype(mc)::value, TT = decltype(tc)::value;
-      if constexpr (BlkC<M, NV, TT>::ok) blk_inv_branch_c<T, L, FMA, NV, M, TT>(Rb, f, acc);
-      else blk_inv_branch<T, L, FMA, NV>(R, lo, vb, m, f, acc);
-    };
-    auto go_m = [&](auto mc) __attribute__((always_inline)) { go(mc, std::integral_constant<int, 0>{}); };
-    (void)tight;  // the tight layout exists only at NV >= 8
-    switch (m) {
-      case 1: go_m(std::integral_constant<int, 1>{}); break;
-      case 2: go_m(std::integral_constant<int, 2>{}); break;
-      case 4: go_m(std::integral_constant<int, 4>{}); break;
-      case 8: go_m(std::integral_constant<int, 8>{}); break;
-      case 16: go_m(std::integral_constant<int, 16>{}); break;
-      case 32: go_m(std::integral_constant<int, 32>{}); break;
-      case 64: go_m(std::integral_constant<int, 64>{}); break;
-      default: blk_inv_branch<T, L, FMA, NV>(R, lo, vb, m, f, acc); break;
-    }
-  }
-}
-
-// The forward (reads t - i*s, both filters from one set of reads): within a tap chunk q runs down so
-// that for every output r the tap i = r - q ascends; chunks ascend.  Input vector u sits at logical
-// u + HLV.
-template <typename T, int L, bool FMA, int NV>
-__device__ __forceinline__ void blk_fwd(const T* X, const BlkLayout& lo, int HLV, int vb, int m, const T* flo,
-                                        const T* fhi, T (&al)[NV][VT<T>::V], T (&ah)[NV][VT<T>::V]) {
-  constexpr int V = VT<T>::V;
-  using vec = typename VT<T>::v;
-  constexpr int TC = blk_chunk<T, NV>();
-#pragma unroll
-  for (int r = 0; r < NV; ++r)
-#pragma unroll
-    for (int e = 0; e < V; ++e) { al[r][e] = T(0); ah[r][e] = T(0); }
-  static_for<0, (L + TC - 1) / TC>([&](auto c) __attribute__((always_inline)) {
-    constexpr int I0 = decltype(c)::value * TC;
-    constexpr int I1 = (I0 + TC < L) ? I0 + TC : L;
-    T fl[I1 - I0], fh[I1 - I0];
-#pragma unroll
-    for (int i = I0; i < I1; ++i) { fl[i - I0] = flo[i]; fh[i - I0] = fhi[i]; }
-#pragma unroll
-    for (int q = NV - 1 - I0; q > -I1; --q) {
-      const vec x = *reinterpret_cast<const vec*>(X + blk_phys(lo, vb + q * m + HLV) * V);
-#pragma unroll
-      for (int r = 0; r < NV; ++r) {
-        const int i = r - q;
-        if (i >= I0 && i < I1) {
-          vmadd<FMA, kPkFwd>(al[r], x, fl[i - I0]);
-          vmadd<FMA, kPkFwd>(ah[r], x, fh[i - I0]);
-        }
-      }
-      if (((NV - 1 - I0 - q) & 3) == 3) __builtin_amdgcn_sched_barrier(0);
-    }
-  });
-#pragma unroll
-  for (int r = 0; r < NV; ++r)
-#pragma unroll
-    for (int e = 0; e < V; ++e) {
-      asm volatile("" : "+v"(al[r][e]));
-      asm volatile("" : "+v"(ah[r][e]));
-    }
-}
-
-// blk_fwd with wave-uniform offsets (as blk_inv_branch_s): Xb = X + blk_phys(layout, vb + HLV) * V, and the
-// read of logical vector vb + HLV + q*m sits off(q) = q*m + ((q*m) >> sh)*pad from it for every thread
-// when the pad groups align with a thread's block and HLV is a multiple of the group (host: vw_plan.cpp blk_plan
-// rounds HLV up to 16 vectors); q*m < 0 shifts arithmetically (floor), as blk_phys does.
-template <typename T, int L, bool FMA, int NV>
-__device__ __forceinline__ void blk_fwd_s(const T* Xb, int m, int sh, int pad, const T* flo, const T* fhi,
-                                          T (&al)[NV][VT<T>::V], T (&ah)[NV][VT<T>::V]) {
-  constexpr int V = VT<T>::V;
-  using vec = typename VT<T>::v;
-  constexpr int TC = blk_chunk<T, NV>();
-#pragma unroll
-  for (int r = 0; r < NV; ++r)
-#pragma unroll
-    for (int e = 0; e < V; ++e) { al[r][e] = T(0); ah[r][e] = T(0); }
-  static_for<0, (L + TC - 1) / TC>([&](auto c) __attribute__((always_inline)) {
-    constexpr int I0 = decltype(c)::value * TC;
-    constexpr int I1 = (I0 + TC < L) ? I0 + TC : L;
-    T fl[I1 - I0], fh[I1 - I0];
-#pragma unroll
-    for (int i = I0; i < I1; ++i) { fl[i - I0] = flo[i]; fh[i - I0] = fhi[i]; }
-#pragma unroll
-    for (int q = NV - 1 - I0; q > -I1; --q) {
-      const int qm = __builtin_amdgcn_readfirstlane(q * m);
-      const int off = __builtin_amdgcn_readfirstlane(qm + (qm >> sh) * pad);
-      const vec x = *reinterpret_cast<const vec*>(Xb + off * V);
-#pragma unroll
-      for (int r = 0; r < NV; ++r) {
-        const int i = r - q;
-        if (i >= I0 && i < I1) {
-          vmadd<FMA, kPkFwd>(al[r], x, fl[i - I0]);
-          vmadd<FMA, kPkFwd>(ah[r], x, fh[i - I0]);
-        }
-      }
-      if (((NV - 1 - I0 - q) & 3) == 3) __builtin_amdgcn_sched_barrier(0);
-    }
-  });
-#pragma unroll
-  for (int r = 0; r < NV; ++r)
-#pragma unroll
-    for (int e = 0; e < V; ++e) {
-      asm volatile("" : "+v"(al[r][e]));
-      asm volatile("" : "+v"(ah[r][e]));
-    }
-}
-
-#ifndef VW_INV_KTAPS
-#define VW_INV_KTAPS -1  // k_inverse_blk: taps from the kernel arguments (SGPRs) instead of LDS; -1: at NV >= 8
-#endif
-
-#ifndef VW_FWD_KTAPS
-#define VW_FWD_KTAPS -1  // k_forward_blk: taps from the kernel arguments (SGPRs) instead of LDS; -1: at NV >= 8 (coif5 NV = 4: neutral)
-#endif
-
-#ifndef VW_BLK_FWD_C
-#define VW_BLK_FWD_C 1  // NV < 8 forward: compile-time stride forms (0: per-lane blk_phys per read)
-#endif
-
-// blk_fwd at a compile-time stride M (NV < 8, as blk_inv_branch_c): with the halo HLV a multiple of 16
-// vectors (host) the physical offset of logical vector vb + HLV + q*M from vb + HLV's is BlkC::off(q)
-// for every thread.  The reads run q = -(L-1) .. NV-1; they are addressed from the lowest one, laundered
-// into a 32-bit LDS base (lds_base: through a plain pointer the compiler re-based most of them, 3 of 63 reads
-// per coif5 fp32 block kept an immediate), so every offset is a non-negative immediate of the ds_read.
-template <typename T, int L, bool FMA, int NV, int M>
-__device__ __forceinline__ void blk_fwd_c(const T* Xb, const T* flo, const T* fhi, T (&al)[NV][VT<T>::V],
-                                          T (&ah)[NV][VT<T>::V]) {
-  constexpr int V = VT<T>::V;
-  using vec = typename VT<T>::v;
-  using C = BlkC<M, NV, 0>;
-  constexpr int TC = blk_chunk<T, NV>();
-  constexpr int QMIN = -(L - 1);
-  const unsigned aq = lds_base(Xb + C::off(QMIN) * V);  // laundered: every read at an immediate offset
-#pragma unroll
-  for (int r = 0; r < NV; ++r)
-#pragma unroll
-    for (int e = 0; e < V; ++e) { al[r][e] = T(0); ah[r][e] = T(0); }
-  static_for<0, (L + TC - 1) / TC>([&](auto c) __attribute__((always_inline)) {
-    constexpr int I0 = decltype(c)::value * TC;
-    constexpr int I1 = (I0 + TC < L) ? I0 + TC : L;
-    T fl[I1 - I0], fh[I1 - I0];
-#pragma unroll
-    for (int i = I0; i < I1; ++i) { fl[i - I0] = flo[i]; fh[i - I0] = fhi[i]; }
-#pragma unroll
-    for (int q = NV - 1 - I0; q > -I1; --q) {
-      const vec x = lds_vec_at<vec>(aq + (unsigned)((C::off(q) - C::off(QMIN)) * V * (int)sizeof(T)));
-#pragma unroll
-      for (int r = 0; r < NV; ++r) {
-        const int i = r - q;
-        if (i >= I0 && i < I1) {
-          vmadd<FMA, kPkFwd>(al[r], x, fl[i - I0]);
-          vmadd<FMA, kPkFwd>(ah[r], x, fh[i - I0]);
-        }
-      }
-      if (((NV - 1 - I0 - q) & 3) == 3) __builtin_amdgcn_sched_barrier(0);
-    }
-  });
-#pragma unroll
-  for (int r = 0; r < NV; ++r)
-#pragma unroll
-    for (int e = 0; e < V; ++e) {
-      asm volatile("" : "+v"(al[r][e]));
-      asm volatile("" : "+v"(ah[r][e]));
-    }
-}
-
-// One forward level at vector stride m >= 1, NV < 8: the compile-time forms for m = 1..64, the generic one
-// otherwise.  Same reads, same sums (bit-identical to blk_fwd).
-template <typename T, int L, bool FMA, int NV>
-__device__ __forceinline__ void blk_fwd_any(const T* X, const BlkLayout& lo, int HLV, int vb, int m, const T* flo,
-                                            const T* fhi, T (&al)[NV][VT<T>::V], T (&ah)[NV][VT<T>::V]) {
-  constexpr int V = VT<T>::V;
-  const T* Xb = X + blk_phys(lo, vb + HLV) * V;
-  auto go = [&](auto mc) __attribute__((always_inline)) {
-    constexpr int M = decltype(mc)::value;
-    if constexpr (BlkC<M, NV, 0>::ok) blk_fwd_c<T, L, FMA, NV, M>(Xb, flo, fhi, al, ah);
-    else blk_fwd<T, L, FMA, NV>(X, lo, HLV, vb, m, flo, fhi, al, ah);
-  };
-  switch (m) {
-    case 1: go(std::integral_constant<int, 1>{}); break;
-    case 2: go(std::integral_constant<int, 2>{}); break;
-    case 4: go(std::integral_constant<int, 4>{}); break;
-    case 8: go(std::integral_constant<int, 8>{}); break;
-    case 16: go(std::integral_constant<int, 16>{}); break;
-    case 32: go(std::integral_constant<int, 32>{}); break;
-    case 64: go(std::integral_constant<int, 64>{}); break;
-    default: blk_fwd<T, L, FMA, NV>(X, lo, HLV, vb, m, flo, fhi, al, ah); break;
-  }
-}
-
-// Forward, PERIODIC, one signal per workgroup: MultiLevelMODWTTransform.decompose (:243-251) /
-// BatchSIMDMODWT.batchMultiLevelMODWTSoA (:362-377) / VectorWaveSwtAdapter forward.  Level inputs in
-// one LDS buffer (p.region1 == 0: two barriers per level) or two (one barrier).  Left wrap images:
-// element t is also the value at t - N.  Host contract: unrolled (L > 0), aligned rows, nvec =
-// threads * NV, nvec a multiple of NV * m_J, no validation / history, p.hlpad = HLV * V.
-template <typename T, int L, bool FMA, int NV>
-__global__ void VW_FUSED_BOUNDS(NV, VW_FUSED_W(L, 8)) k_forward_blk(const FwdArgs<T> p) {
-  constexpr int V = VT<T>::V;
-  using vec = typename VT<T>::v;
-  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  T* X = reinterpret_cast<T*>(smem);
-  T* Y = p.region1 ? X + p.region1 : X;
-  const bool dbl = p.region1 != 0;
-  const long long b = blockIdx.x;
-  // the taps live in LDS (p.tap_lds): read per level and chunk, never hoisted out of the level loop --
-  // all 2L taps of a long filter held in registers across it spill (60 for coif5)
-  T* const taps = reinterpret_cast<T*>(smem) + p.tap_lds;
-  for (int i = threadIdx.x; i < 2 * L; i += blockDim.x) taps[i] = i < L ? p.lo[i] : p.hi[i - L];
-  // kernel-argument taps (scalar loads, SGPR operands) at NV = 8 as in k_inverse_blk: fp64 L = 16 128 VGPRs
-  // + 12 B/lane of scratch -> 99, none
-  constexpr bool ktaps = VW_FWD_KTAPS < 0 ? NV >= 8 : VW_FWD_KTAPS != 0;
-  const T* const flo = ktaps ? p.lo : taps;
-  const T* const fhi = ktaps ? p.hi : taps + L;
-  const int N = p.N;
-  const int nvec = N / V;
-  const int NT = blockDim.x;
-  const int tid = threadIdx.x;
-  const int HLV = p.hlpad / V;
-  auto m_of = [&](int j) { return p.lv[j - 1].s / V; };
-  auto hlv_of = [&](int j) { return ((L - 1) * p.lv[j - 1].s + V - 1) / V; };
-  // vector w of level j's input (+ its left wrap image)
-  auto put = [&](T* buf, int j, int w, const vec& o) {
-    const BlkLayout lo = blk_layout(m_of(j), NV, p.blk_tight);
-    blk_store<T>(buf, lo, w + HLV, o);
-    if (w >= nvec - hlv_of(j)) blk_store<T>(buf, lo, w - nvec + HLV, o);
-  };
-  {
-    T r0[NV][V];
-    load_row_regs<T, NV>(r0, p.x + b * p.ldx, N, nvec, true, false);
-    wait_vmem();
-#pragma unroll
-    for (int k = 0; k < NV; ++k) {
-      int w = tid + k * NT;
-      asm volatile("" : "+v"(w));
-      vec o;
-#pragma unroll
-      for (int e = 0; e < V; ++e) o[e] = r0[k][e];
-      put(X, 1, w, o);
-      __builtin_amdgcn_sched_barrier(0);
-    }
-  }
-  T nf = T(0);  // VW_FLAG_REF_NONFINITE: a_J's probe (as k_forward_persist)
-  for (int j = 1; j <= p.J; ++j) {
-    const int m = m_of(j);
-    lds_barrier();  // X = level input + images; every read of Y (previous level) done
-    T* dout = p.details + ((size_t)(j - 1) * (size_t)p.B + (size_t)b) * (size_t)N;
-    T* aout = p.approx + b * (size_t)N;
-    const bool last = j == p.J;
-    T al[NV][V], ah[NV][V];
-    int vb = 0;
-    if (m) {
-      vb = blk_base<NV>(m);
-      const BlkLayout lo = blk_layout(m, NV, p.blk_tight);
-      const int sh = __builtin_amdgcn_readfirstlane(lo.sh), pad = __builtin_amdgcn_readfirstlane(lo.pad);
-      bool fc = false;
-      if constexpr (NV < 8) {
-        if (VW_BLK_FWD_C && (HLV & 15) == 0) {
-          blk_fwd_any<T, L, FMA, NV>(X, lo, HLV, vb, m, flo, fhi, al, ah);
-          fc = true;
-        }
-      }
-      if (fc) {
-      } else if (VW_BLK_SOFF && NV >= 8 && (pad == 0 || (((m * NV) & ((1 << sh) - 1)) == 0 && (HLV & ((1 << sh) - 1)) == 0)))
-        blk_fwd_s<T, L, FMA, NV>(X + blk_phys(lo, vb + HLV) * V, m, sh, pad, flo, fhi, al, ah);
-      else
-        blk_fwd<T, L, FMA, NV>(X, lo, HLV, vb, m, flo, fhi, al, ah);
-      if (m < VW_BLK_NT_M) {
-        // a lane's outputs are m*16-byte pieces NV*m*16 bytes apart: write-back stores, so that L2
-        // merges a line's pieces before it goes to HBM (nontemporal stores of 16-byte pieces wrote
-        // 1.5x the algorithmic bytes on coif5 fp32, profiles/hbm_traffic_coif5-f32.json)
-#pragma unroll
-        for (int r = 0; r < NV; ++r) {
-          store_vec<0>(dout, (vb + r * m) * V, N, true, ah[r]);
-          if (last) store_vec<0>(aout, (vb + r * m) * V, N, true, al[r]);
-        }
-      } else {
-#pragma unroll
-        for (int r = 0; r < NV; ++r) {
-          store_vec<VW_FWD_STORE_AUX>(dout, (vb + r * m) * V, N, true, ah[r]);
-          if (last) store_vec<VW_FWD_STORE_AUX>(aout, (vb + r * m) * V, N, true, al[r]);
-        }
-      }
-    } else {
-      // s < V (m == 0): only the register-window forms.  (fwd_row's strided form, unreachable here,
-      // kept all 2L taps of its loop live and spilled coif5 fp32: 193 VGPRs of scratch, 1.5x the
-      // kernel's HBM write bytes -- profiles/r02/hbm_traffic_coif5-f32.json.)
-      auto em = [&](int k, int w, const T (&l)[V], const T (&h)[V]) {
-        store_vec<VW_FWD_STORE_AUX>(dout, w * V, N, true, h);
-        if (last) store_vec<VW_FWD_STORE_AUX>(aout, w * V, N, true, l);
-#pragma unroll
-        for (int e = 0; e < V; ++e) { al[k][e] = l[e]; ah[k][e] = h[e]; }
-      };
-      if constexpr (V == 4) {
-        if (p.lv[j - 1].s == 2) fwd_row_t<T, L, FMA, NV, 2>(X + HLV * V, nvec, 2, flo, fhi, p.taps, em);
-        else fwd_row_t<T, L, FMA, NV, 1>(X + HLV * V, nvec, 1, flo, fhi, p.taps, em);
-      } else {
-        fwd_row_t<T, L, FMA, NV, 1>(X + HLV * V, nvec, 1, flo, fhi, p.taps, em);
-      }
-    }
-    if (p.nf_flag && last) {
-#pragma unroll
-      for (int r = 0; r < NV; ++r) nf_probe<T, V>(nf, al[r]);
-    }
-    if (!last) {
-      if (!dbl) lds_barrier();  // one buffer: every read of this level's input done first
-#pragma unroll
-      for (int r = 0; r < NV; ++r) {
-        int w = m ? vb + r * m : tid + r * NT;
-        asm volatile("" : "+v"(w));
-        vec o;
-#pragma unroll
-        for (int e = 0; e < V; ++e) o[e] = al[r][e];
-        put(Y, j + 1, w, o);
-        __builtin_amdgcn_sched_barrier(0);
-      }
-      T* t = X; X = Y; Y = t;
-    }
-  }
-  if (p.nf_flag) nf_flag_row<T>(p.nf_flag, b, nf);
-}
-
-// Inverse, PERIODIC, sequential sums (K4), one region time-shared as k_inverse_seq.  Right wrap
-// images: element t is also the value at t + N.  Host contract as k_forward_blk (hlpad = 0).
-template <typename T, int L, bool FMA, int NV>
-__global__ void VW_FUSED_BOUNDS(NV, VW_FUSED_W(L, 6)) k_inverse_blk(const InvArgs<T> p) {
-  constexpr int V = VT<T>::V;
-  using vec = typename VT<T>::v;
-  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  T* R = reinterpret_cast<T*>(smem);
-  const long long b = p.rev ? p.B - 1 - (long long)blockIdx.x : (long long)blockIdx.x;
-  const int N = p.N;
-  const int nvec = N / V;
-  const int NT = blockDim.x;
-  const int tid = threadIdx.x;
-  T* const taps = reinterpret_cast<T*>(smem) + p.tap_lds;  // as k_forward_blk
-  for (int i = tid; i < 2 * L; i += NT) taps[i] = i < L ? p.lo[i] : p.hi[i - L];
-  // NV = 8 (sym8 fp64 at N = 16384): the taps from the kernel arguments -- scalar loads, SGPR operands of the
-  // FMAs -- free the VGPRs that held them (128 + 12-40 B/lane of scratch -> 123-125, none) and the LDS tap
-  // reads: inverse 6.72-6.77 -> 6.27-6.32 ms.  NV = 4 (coif5 fp32) keeps them in LDS: there the freed VGPRs
-  // admit a third workgroup per CU and the inverse slows, 6.73-6.80 -> 6.94-6.96 ms
-  // (profiles/r04/ab_ktaps_coif5_sym8.log)
-  constexpr bool ktaps = VW_INV_KTAPS < 0 ? NV >= 8 : VW_INV_KTAPS != 0;
-  const T* const flo = ktaps ? p.lo : taps;
-  const T* const fhi = ktaps ? p.hi : taps + L;
-  auto thr_of = [&](int j) { return p.thr ? load_uniform(p.thr + (size_t)(j - 1) * (size_t)p.thr_ld + (size_t)b) : T(0); };
-  const size_t plane = (size_t)p.B * (size_t)N;
-  auto m_of = [&](int j) { return p.lv[j - 1].s / V; };
-  auto hrv_of = [&](int j) { return ((L - 1) * p.lv[j - 1].s + V - 1) / V; };
-  auto put = [&](int j, int w, const vec& o) {
-    const BlkLayout lo = blk_layout(m_of(j), NV, p.blk_tight);
-    blk_store<T>(R, lo, w, o);
-    if (w < hrv_of(j)) blk_store<T>(R, lo, w + nvec, o);
-  };
-  // a row held in the standard mapping (w = tid + k*NT) into level j's layout; MODE as regs_to_level_m
-  auto stage_std = [&](const T (&r)[NV][V], int j, int mode, T thr_b) {
-#pragma unroll
-    for (int k = 0; k < NV; ++k) {
-      int w = tid + k * NT;
-      asm volatile("" : "+v"(w));
-      vec o;
-#pragma unroll
-      for (int e = 0; e < V; ++e) {
-        if (mode == 1) o[e] = T(0);
-        else if (mode == 2) o[e] = threshold_t(r[k][e], thr_b, p.soft);
-        else o[e] = r[k][e];
-      }
-      put(j, w, o);
-      __builtin_amdgcn_sched_barrier(0);
-    }
-  };
-
-  T acc[NV][V];
-  T dreg[NV][V];
-  load_row_regs<T, NV>(acc, p.approx + b * (size_t)N, N, nvec, true, p.approx_zero != 0);
-  load_row_regs<T, NV>(dreg, p.details + (size_t)(p.J - 1) * plane + b * (size_t)N, N, nvec, true,
-                       p.lv[p.J - 1].use_d == 0);
-  wait_vmem();
-  stage_std(acc, p.J, p.approx_zero ? 1 : 0, T(0));
-
-  for (int j = p.J; j >= 1; --j) {
-    const LevelDesc lv = p.lv[j - 1];
-    const int m = m_of(j);
-    const BlkLayout lo = blk_layout(m, NV, p.blk_tight);
-    const int vb = m ? blk_base<NV>(m) : 0;
-    lds_barrier();  // R = a_j + wrap images
-    zero_regs<T, NV>(acc);
-    if (m) blk_inv_any<T, L, FMA, NV>(R, lo, p.blk_tight, vb, m, flo, acc);
-    else inv_row<T, L, FMA, NV>(R, nvec, lv.s, 1, 0, flo, p.taps, 0, acc);
-    lds_barrier();  // every approximation-branch read done
-    wait_vmem();    // the d_j prefetch
-    stage_std(dreg, j, lv.use_d == 0 ? 1 : (p.thr ? 2 : 0), thr_of(j));
-    if (j > 1)
-      load_row_regs<T, NV>(dreg, p.details + (size_t)(j - 2) * plane + b * (size_t)N, N, nvec, true,
-                           p.lv[j - 2].use_d == 0);
-    lds_barrier();  // R = d_j + wrap images
-    if (m) blk_inv_any<T, L, FMA, NV>(R, lo, p.blk_tight, vb, m, fhi, acc);
-    else inv_row<T, L, FMA, NV>(R, nvec, lv.s, 1, 0, fhi, p.taps, 0, acc);
-    if (j > 1) {
-      lds_barrier();  // every detail-branch read done
-#pragma unroll
-      for (int r = 0; r < NV; ++r) {
-        int w = m ? vb + r * m : tid + r * NT;
-        asm volatile("" : "+v"(w));
-        vec o;
-#pragma unroll
-        for (int e = 0; e < V; ++e) o[e] = acc[r][e];
-        put(j - 1, w, o);
-        __builtin_amdgcn_sched_barrier(0);
-      }
-    }
-  }
-  // level 1 (s = 1 < V) ran in the standard mapping: coalesced stores
-#pragma unroll
-  for (int k = 0; k < NV; ++k) store_vec<VW_INV_STORE_AUX>(p.y + b * (size_t)N, (tid + k * NT) * V, N, true, acc[k]);
-  if (p.nf_flag) {  // VW_FLAG_REF_NONFINITE: y's probe (as k_inverse_seq)
-    T nf = T(0);
-#pragma unroll
-    for (int k = 0; k < NV; ++k) nf_probe<T, V>(nf, acc[k]);
-    nf_flag_row<T>(p.nf_flag, b, nf);
-  }
-}
+namespace vw {
 
 // ---------------------------------------------------------------------------------------------
 // Per-level tiled kernels (signals longer than the fused kernels hold in LDS).  One workgroup per
@@ -2530,9 +1860,6 @@ __global__ void __launch_bounds__(256) k_forward_multi(const MultiArgs<T> p) {
 // workgroups fit a CU (a third region for a_{j-1} measured 1.2x slower: two per CU).  NI = 4 (fp64, host
 // policy) on a tile whose register-blocked levels give all four waves work: at NI = 8 a 2048-sample db8
 // tile had 129-144 threads of work per level, one SIMD idle and one mostly idle.
-#ifndef VW_MULTI_CK
-#define VW_MULTI_CK 1  // k_inverse_multi register-blocked levels: compile-time strides, immediate LDS offsets
-#endif
 template <typename T, int L, bool FMA, int NI = kMultiInvNI>
 __global__ void __launch_bounds__(256) k_inverse_multi(const MultiArgs<T> p) {
   constexpr int V = VT<T>::V;
@@ -2558,12 +1885,12 @@ __global__ void __launch_bounds__(256) k_inverse_multi(const MultiArgs<T> p) {
   // Padded LDS layout (p.pad, host contract: pf and rblk on): the register-blocked levels (vector
   // stride m = s/V in 1..8) read lanes NI*m vectors apart -- an 8-way bank conflict at m = 1 in the
   // natural layout (62 % of LDS cycles in conflicts on db8 levels 1-5, profiles/r03/pmc_db8_stream.txt).
-  // Level k's A and D then hold logical vector u at u + u/8 at NI = 8 (layout 1), at NI = 4 at u + u/4
-  // (m <= 4, layout 2) or u + 2*(u/8) (m = 8, layout 3) -- blk_layout's NV = 8 / NV = 4 layouts, conflict-free
-  // ds_read_b128 at every m <= 8 under the gfx950 lane groups; levels with m = 0 or m >= 16 keep the natural
-  // layout (0).
+  // Level k's A and D then hold logical vector u at u + u/8 at NI = 8, at NI = 4 at u + u/4
+  // (m <= 4) or u + 2*(u/8) (m = 8) -- blk_pad's NV = 8 / NV = 4 layouts, conflict-free ds_read_b128 at every
+  // m <= 8 under the gfx950 lane groups; levels with m = 0 or m >= 16 keep the natural layout.
   // (a layout is (shift, pad): u -> u + (u >> shift) * pad -- one formula, no per-layout copies of the
   // hoisted store addresses)
+  // The rule is blk_pad (vw_internal.h), restated: through blk_pad this run-time form compiled to other code.
   auto layout = [&](int k) {
     const int sk = p.s0 << k, m = sk / V;
     int2 lay = make_int2(30, 0);
@@ -2668,27 +1995,22 @@ __global__ void __launch_bounds__(256) k_inverse_multi(const MultiArgs<T> p) {
 #pragma unroll
           for (int e = 0; e < V; ++e) acc[r][e] = T(0);
         if (pr < pairs) {
-          // compile-time stride M and layout LC: the reads of a lane sit at fixed offsets off(j) from
-          // phys(vb) -- with G = 8 (layouts 1, 3) or 4 (layout 2) vectors per pad group, (vb % G) + (M*j % G) < G
+          // compile-time stride M and its layout (BlkC, vw_blk.h): the reads of a lane sit at fixed offsets off(j)
+          // from phys(vb) -- with G = 8 or 4 (NI = 4, M <= 4) vectors per pad group, (vb % G) + (M*j % G) < G
           // for every M <= 8 here (vb % G = pr % M < M, or M*j % G = 0), so (vb + M*j) / G = vb / G + M*j / G --
           // and each is one ds_read at an immediate offset.
           // Reads past the region end (at most 15*M vectors, only for outputs that are never stored) stay
           // inside the allocation: the host adds p.slack >= 16*8 + 16 vectors after D (M <= 8 here).
           const T* const tlo = p.lo;
           const T* const thi = p.hi;
-          auto blk_c = [&](auto mc, auto lc) __attribute__((always_inline)) {
-            constexpr int M = decltype(mc)::value;
-            constexpr int PD = decltype(lc)::value;
-            constexpr auto off = [](int j) {
-              return PD == 1 ? M * j + ((M * j) >> 3) : PD == 2 ? M * j + ((M * j) >> 2) : M * j + (((M * j) >> 3) << 1);
-            };
+          auto blk_c = [&](auto mc) __attribute__((always_inline)) {
+            using C = BlkC<decltype(mc)::value, NI, 0>;  // the padded layout of stride M (p.pad)
 #pragma unroll
             for (int br = 0; br < 2; ++br) {
-              const unsigned ab = lds_base((br == 0 ? A : D) + phys(vb, PD == 1 ? make_int2(3, 1) : PD == 2 ? make_int2(2, 1)
-                                                                                        : make_int2(3, 2)) * V);
+              const unsigned ab = lds_base((br == 0 ? A : D) + phys(vb, make_int2(C::SH, C::PAD)) * V);
 #pragma unroll
               for (int j = 0; j < NI + L - 1; ++j) {
-                const vec x = lds_vec_at<vec>(ab + (unsigned)(off(j) * V * (int)sizeof(T)));
+                const vec x = lds_vec_at<vec>(ab + (unsigned)(C::off(j) * V * (int)sizeof(T)));
 #pragma unroll
                 for (int r = 0; r < NI; ++r) {
                   const int i = j - r;
@@ -2708,17 +2030,15 @@ __global__ void __launch_bounds__(256) k_inverse_multi(const MultiArgs<T> p) {
           using I2 = std::integral_constant<int, 2>;
           using I4 = std::integral_constant<int, 4>;
           using I8 = std::integral_constant<int, 8>;
-          using P1 = std::integral_constant<int, NI >= 8 ? 1 : 2>;  // layout of m = 1, 2, 4
-          using P8 = std::integral_constant<int, NI >= 8 ? 1 : 3>;  // layout of m = 8
           // padded layouts only (the default, p.pad): more instantiations in this function raised it from 160
           // VGPRs to 238 + 1.3 KiB of scratch (the taps, hoisted across the switch)
-          const int sel = VW_MULTI_CK && p.slack && padded(pdk) ? m : -1;
+          const int sel = p.slack && padded(pdk) ? m : -1;
           switch (sel) {
-            case 1: blk_c(I1{}, P1{}); break;
-            case 2: blk_c(I2{}, P1{}); break;
-            case 4: blk_c(I4{}, P1{}); break;
-            case 8: blk_c(I8{}, P8{}); break;
-            default:
+            case 1: blk_c(I1{}); break;
+            case 2: blk_c(I2{}); break;
+            case 4: blk_c(I4{}); break;
+            case 8: blk_c(I8{}); break;
+            default:  // (its own copy of blk_c's loop: one loop given a reader and a tap accessor compiled to other code)
 #pragma unroll
               for (int br = 0; br < 2; ++br) {
                 const T* buf = br == 0 ? A : D;

@@ -244,12 +244,12 @@ static void set_halo_images(LevelDesc& d, int64_t N, int64_t npow2, int V, int t
   d.own = (d.hl <= N && d.hr <= N && d.vs <= threads && (int64_t)d.ve >= (int64_t)(nv - 1) * threads) ? 1 : 0;
 }
 
-// Padded LDS layout of the register-blocked PERIODIC kernels (vw_device.h k_forward_blk / k_inverse_blk),
+// Padded LDS layout of the register-blocked PERIODIC kernels (vw_blk.h k_forward_blk / k_inverse_blk),
 // one rule for both directions.  The forward keeps one left halo for all levels (whole pad groups of 16
 // vectors where they fit: the kernel then reads at wave-uniform (NV = 8) or compile-time (NV = 4) offsets);
 // the inverse a right halo per level.  `ok`: every level PERIODIC in the +1 / 0 orientation, the rows
 // divide into blocks of NV * m_J vectors, the halo lies within the row and the buffer (inverse: + tap table) fits LDS.
-// `tight`: sparse padding (blk_layout) so that an NV = 8 level fits (sym8 at N = 16384); the forward
+// `tight`: sparse padding (blk_pad) so that an NV = 8 level fits (sym8 at N = 16384); the forward
 // reports it even where the layout is not used, as its argument struct always has.
 struct BlkPlan {
   bool ok;
@@ -274,10 +274,9 @@ static BlkPlan blk_plan(const LevelDesc* lv, int J, int L, int64_t nvec, int nv,
   int64_t buf[2] = {0, 0};
   for (int j = 0; j < J; ++j)
     for (int tight = 0; tight < 2; ++tight) {
-      int sh, pd;
-      blk_layout_host(lv[j].s / V, nv, &sh, &pd, tight);
+      const BlkLayout lo = blk_pad(lv[j].s / V, nv, tight);
       const int64_t u = nvec + (inverse ? halo[j] : hmax) - 1;
-      buf[tight] = std::max(buf[tight], u + (u >> sh) * pd + 1);
+      buf[tight] = std::max(buf[tight], u + (u >> lo.sh) * lo.pad + 1);
     }
   const bool roomy = buf[0] * 16 + taps_b <= kLdsBytes;
   r.tight = (nv >= 8 && !roomy && (!inverse || (r.ok && buf[1] * 16 + taps_b <= kLdsBytes))) ? 1 : 0;
@@ -531,7 +530,7 @@ static bool plan_forward_fused(const Tuning& tu, const FwdCall<T>& c, int max_hl
   // ab_overlap_direct_512.log)
   a.dma_nt = tu.dma_nt >= 0 ? tu.dma_nt : (c.B <= 2LL * c.cus ? 1 : 0);
   p->kernel = (dbl && a.unrolled && persist_ok(threads, nv, fit)) ? kFwdPersist : kFwdFused;
-  // register-blocked PERIODIC forward for long filters (vw_device.h k_forward_blk): padded layouts
+  // register-blocked PERIODIC forward for long filters (vw_blk.h k_forward_blk): padded layouts
   // (NV = 8, 1024-thread workgroups: with its taps from the kernel arguments (round 4, 99 VGPRs, no
   // spills) the blocked forward beats the fused one at sym8 N = 16384: 5.27-5.29 -> 4.76 ms,
   // profiles/r04/ab_blk_fwd8_ktaps_sym8.log; VW_BLK_FWD8=0 restores the fused kernel)
@@ -813,7 +812,7 @@ static bool plan_inverse_fused(const Tuning& tu, const InvCall<T>& c, bool pair,
   a.level_ct = tu.level_ct;
   a.full = tu.level_ct && a.unrolled && (int64_t)threads * nv == nvec;
   p->kernel = pair ? kInvPair : db ? kInvDb : kInvSeq;
-  // register-blocked PERIODIC inverse for long filters (vw_device.h k_inverse_blk)
+  // register-blocked PERIODIC inverse for long filters (vw_blk.h k_inverse_blk)
   if (tu.blk > 0 && L >= tu.blk && has_unrolled_taps(L) && nv != 2 && !pair && !db && periodic && a.unrolled &&
       (int64_t)threads * nv == nvec) {
     const BlkPlan b = blk_plan<T>(a.lv, J, L, nvec, nv, true);
