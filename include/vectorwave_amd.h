@@ -205,6 +205,61 @@ VW_API vw_status vw_modwt_inverse_f32(vw_ctx *ctx, const float *details, const f
                                       int wavelet_id, int boundary, int J, unsigned detail_mask,
                                       int approx_zero, unsigned flags, float *y);
 
+/* ---- biorthogonal banks: two filter lengths -----------------------------------------------------
+ * BiorthogonalSpline.BIOR1_1 .. BIOR6_8 and ReverseBiorthogonalSpline.RBIO1_1 .. RBIO6_8
+ * (core/api/BiorthogonalSpline.java:304-339, ReverseBiorthogonalSpline.java:107-128): the low-pass has Llo
+ * taps, the high-pass Lhi, 1 <= Llo, Lhi <= 64 (else VW_ERR_ARG).  The caller passes the ANALYSIS pair
+ * (lowPassDecomposition / highPassDecomposition) to the forward calls and the SYNTHESIS pair
+ * (lowPassReconstruction / highPassReconstruction) to the inverse calls; wavelet_id is VW_WID_OTHER for these
+ * families.  Every other argument, the layouts and the flags VALIDATE / HOST_MEMORY / SYNC / FMA /
+ * REF_NONFINITE are those of the equal-length calls, and with Llo == Lhi each call IS its equal-length
+ * counterpart (same plan, same bits).  What the reference does with two lengths, restated:
+ *   forward           each filter over its own upsampled length, ascending taps (:731-754).
+ *   CORE_LEVELS       J > vw_max_levels(N, Llo) -> VW_ERR_LEVEL (the cap reads the low-pass alone, :455-501);
+ *                     max(Llo_J, Lhi_J) > N -> VW_ERR_TOO_LARGE (:717-729, :561-574).  Without the flag: the
+ *                     equal-length call's checks with L = max(Llo, Lhi).
+ *   inverse PERIODIC  every low tap, then every high tap, one accumulator (:578-588).
+ *   inverse SYMMETRIC decide() keys on Llo; the approximation branch shifts by tau(Llo) + dH, the detail
+ *                     branch by tau(Lhi) + dG (:604-608).
+ *   pairwise inverses (ZERO_PADDING multi-level :591-601; vw_modwt1_inverse in every mode, MODWTTransform.java
+ *                     :203-299) loop over l < Llo_j and read high[l]: with Lhi >= Llo only the high taps
+ *                     i < Llo are used (the reference's truncation); with Lhi < Llo the reference indexes past
+ *                     its high-pass array (ArrayIndexOutOfBoundsException) -> VW_ERR_UNSUPPORTED.
+ *   VW_FLAG_FFT_SWITCH the outer gate reads Llo_j, behind it each filter takes the FFT branch by its own
+ *                     length (WaveletOperations.java:31-33).  A level of a non-power-of-two N >= 1024 where
+ *                     exactly one filter does ("mixed level") is not implemented -> VW_ERR_UNSUPPORTED naming
+ *                     the level; where both or neither do, the call runs as the equal-length one.
+ * Without VW_FLAG_REF_NONFINITE, outputs whose window reaches a non-finite value are unspecified (the shorter
+ * filter runs zero-extended: its absent taps multiply as zeros).  reconstructionScale / groupDelay are not
+ * part of any MODWT path and are not applied.  Context option VW_BI (bit 0 forward, bit 1
+ * inverse; 0 = neither): the fused kernels run each filter at its own tap count instead of zero-extending the
+ * shorter one (same bits).  The default, 3, does so only for the pairs with compile-time kernels -- (9,7), (7,9),
+ * (5,3), (3,5): bior4.4 / rbio4.4, bior2.2 / rbio2.2 -- and leaves EVERY OTHER PAIR on the zero-extended route;
+ * bit 2 (VW_BI=7) runs those on the two-length runtime-tap bodies too, measured about 3 x slower than that route.
+ * VW_BI_LISTED=0: the kernels run max(Llo, Lhi) taps
+ * even where that count has no tap-unrolled kernels (default: one more zero tap where that reaches one; same bits). */
+VW_API vw_status vw_modwt_forward_bi_f64(vw_ctx *ctx, const double *x, int64_t B, int64_t N, int64_t ldx,
+                                         const double *lo, int Llo, const double *hi, int Lhi, int wavelet_id,
+                                         int boundary, int J, unsigned flags, double *details, double *approx);
+VW_API vw_status vw_modwt_forward_bi_f32(vw_ctx *ctx, const float *x, int64_t B, int64_t N, int64_t ldx,
+                                         const double *lo, int Llo, const double *hi, int Lhi, int wavelet_id,
+                                         int boundary, int J, unsigned flags, float *details, float *approx);
+VW_API vw_status vw_modwt_inverse_bi_f64(vw_ctx *ctx, const double *details, const double *approx, int64_t B,
+                                         int64_t N, const double *lo, int Llo, const double *hi, int Lhi,
+                                         int wavelet_id, int boundary, int J, unsigned detail_mask,
+                                         int approx_zero, unsigned flags, double *y);
+VW_API vw_status vw_modwt_inverse_bi_f32(vw_ctx *ctx, const float *details, const float *approx, int64_t B,
+                                         int64_t N, const double *lo, int Llo, const double *hi, int Lhi,
+                                         int wavelet_id, int boundary, int J, unsigned detail_mask,
+                                         int approx_zero, unsigned flags, float *y);
+/* single level (vw_modwt1_*): MODWTTransform.forward convolves each filter on its own; its inverse is pairwise */
+VW_API vw_status vw_modwt1_forward_bi_f64(vw_ctx *ctx, const double *x, int64_t B, int64_t N, int64_t ldx,
+                                          const double *lo, int Llo, const double *hi, int Lhi, int boundary,
+                                          unsigned flags, double *approx, double *detail);
+VW_API vw_status vw_modwt1_inverse_bi_f64(vw_ctx *ctx, const double *approx, const double *detail, int64_t B,
+                                          int64_t N, const double *lo, int Llo, const double *hi, int Lhi,
+                                          int boundary, unsigned flags, double *y);
+
 /* ---- wavelet energy per level --------------------------------------------------------------------
  * MultiLevelMODWTResult.getApproximationEnergy / getDetailEnergyAtLevel / getRelativeEnergyDistribution
  * (core/modwt/MultiLevelMODWTResultImpl.java:91-139, computeEnergy :211-216; MutableMultiLevelMODWTResultImpl

@@ -62,7 +62,8 @@ public final class AmdBatchMODWT {
         checkBatchReach(wavelet, n, levels);
         double[][][] details = new double[levels][batch][n];
         double[][] approx = new double[batch][n];
-        AmdNative.check(AmdNative.modwtForwardAoS(AmdRuntime.ctx(), signals, wavelet.lowPassDecomposition(),
+        // (a BiorthogonalWavelet, whose two filters differ in length, goes through modwtForwardBiAoS)
+        AmdNative.check(AmdNative.forwardAoS(AmdRuntime.ctx(), signals, wavelet.lowPassDecomposition(),
                 wavelet.highPassDecomposition(), AmdNative.waveletId(wavelet), 0, levels,
                 AmdRuntime.FMA | AmdNative.FLAG_REF_NONFINITE, details, approx));
         return new BatchMODWT.MultiLevelResult(details, approx);
@@ -134,7 +135,7 @@ public final class AmdBatchMODWT {
         }
         double[][] out = new double[batch][n];
         // core MultiLevelMODWTTransform.reconstruct: its level semantics (FLAG_CORE_LEVELS)
-        AmdNative.check(AmdNative.modwtInverseAoS(AmdRuntime.ctx(), detailPerLevel, finalApprox,
+        AmdNative.check(AmdNative.inverseAoS(AmdRuntime.ctx(), detailPerLevel, finalApprox,
                 wavelet.lowPassReconstruction(), wavelet.highPassReconstruction(), AmdNative.waveletId(wavelet), 0,
                 AmdRuntime.FMA | AmdNative.FLAG_CORE_LEVELS | AmdNative.FLAG_REF_NONFINITE, out));
         return out;

@@ -86,7 +86,8 @@ public final class AmdMultiLevelMODWT {
         double[][] app = new double[batch][n];
         final int flags = AmdNative.FLAG_CORE_LEVELS | AmdNative.FLAG_VALIDATE | AmdNative.FLAG_FFT_SWITCH
                 | AmdRuntime.FMA;
-        AmdNative.check(AmdNative.modwtForwardAoS(AmdRuntime.ctx(), signals, wavelet.lowPassDecomposition(),
+        // (a BiorthogonalWavelet, whose two filters differ in length, goes through modwtForwardBiAoS)
+        AmdNative.check(AmdNative.forwardAoS(AmdRuntime.ctx(), signals, wavelet.lowPassDecomposition(),
                 wavelet.highPassDecomposition(), AmdNative.waveletId(wavelet), boundary, levels, flags, det, app));
         MultiLevelMODWTResult[] out = new MultiLevelMODWTResult[batch];
         for (int b = 0; b < batch; b++) {
@@ -176,6 +177,20 @@ public final class AmdMultiLevelMODWT {
     private double[] inverse(MultiLevelMODWTResult r, int mask, boolean approxZero) {
         final int J = r.getLevels();
         final int n = r.getSignalLength();
+        final double[] rlo = wavelet.lowPassReconstruction(), rhi = wavelet.highPassReconstruction();
+        if (rlo.length != rhi.length) {
+            // a BiorthogonalWavelet: the two-length native takes whole planes, so a masked level is passed as the
+            // zero row the engine would read for it, and a dropped approximation as a zero row
+            double[][][] d = new double[J][1][];
+            for (int l = 1; l <= J; l++) {
+                d[l - 1][0] = ((mask >>> (l - 1)) & 1) != 0 ? r.getDetailCoeffsAtLevel(l) : new double[n];
+            }
+            double[][] a = {approxZero ? new double[n] : r.getApproximationCoeffs()};
+            double[][] out = new double[1][n];
+            AmdNative.check(AmdNative.modwtInverseBiAoS(AmdRuntime.ctx(), d, a, rlo, rhi, AmdNative.waveletId(wavelet),
+                    boundary, AmdNative.FLAG_CORE_LEVELS | AmdNative.FLAG_REF_NONFINITE | AmdRuntime.FMA, out));
+            return out[0];
+        }
         double[] det = new double[Math.multiplyExact(J, n)];
         for (int l = 1; l <= J; l++) {
             System.arraycopy(r.getDetailCoeffsAtLevel(l), 0, det, (l - 1) * n, n);

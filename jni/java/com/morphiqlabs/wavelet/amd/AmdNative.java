@@ -103,6 +103,29 @@ public final class AmdNative {
                                       int waveletId, int boundary, int flags, double[][] y);
     static native int swtDenoiseAoS(long ctx, double[][] x, double[] lo, double[] hi, int waveletId, int boundary,
                                     int J, double threshold, boolean soft, int flags, double[][] y);
+    // Biorthogonal banks (BiorthogonalSpline / ReverseBiorthogonalSpline): lo and hi of different lengths, the
+    // analysis pair forward, the synthesis pair back (vw_modwt_forward_bi_f64 / vw_modwt_inverse_bi_f64); chunking
+    // and error messages as the two natives above
+    static native int modwtForwardBiAoS(long ctx, double[][] x, double[] lo, double[] hi, int waveletId, int boundary,
+                                        int J, int flags, double[][][] details, double[][] approx);
+    static native int modwtInverseBiAoS(long ctx, double[][][] details, double[][] approx, double[] lo, double[] hi,
+                                        int waveletId, int boundary, int flags, double[][] y);
+
+    /** modwtForwardAoS, or its two-length form when the bank's filters differ in length (a BiorthogonalWavelet). */
+    static int forwardAoS(long ctx, double[][] x, double[] lo, double[] hi, int waveletId, int boundary, int J,
+                          int flags, double[][][] details, double[][] approx) {
+        return lo.length != hi.length
+                ? modwtForwardBiAoS(ctx, x, lo, hi, waveletId, boundary, J, flags, details, approx)
+                : modwtForwardAoS(ctx, x, lo, hi, waveletId, boundary, J, flags, details, approx);
+    }
+
+    /** modwtInverseAoS, or its two-length form when the bank's filters differ in length. */
+    static int inverseAoS(long ctx, double[][][] details, double[][] approx, double[] lo, double[] hi, int waveletId,
+                          int boundary, int flags, double[][] y) {
+        return lo.length != hi.length
+                ? modwtInverseBiAoS(ctx, details, approx, lo, hi, waveletId, boundary, flags, y)
+                : modwtInverseAoS(ctx, details, approx, lo, hi, waveletId, boundary, flags, y);
+    }
 
     // energy per level of every signal (out: (levels + 1) * B doubles, [approx, d1..dJ][B]): of the forward of the
     // rows, and of coefficient planes the caller already has (details [J][B][N], approx [B][N])

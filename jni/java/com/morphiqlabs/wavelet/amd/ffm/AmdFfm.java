@@ -40,6 +40,8 @@ public final class AmdFfm implements AutoCloseable {
     private final SymbolLookup lib;
     private final MethodHandle ctxCreate, ctxDestroy, ctxSync, lastError, forward, inverse, denoise, devAlloc,
             devFree, memcpy, pipeCreate, pipeRun, pipeJoin, pipeDestroy;
+    /** Declared only: vw_modwt_{forward,inverse}_bi_f64 for banks whose low-pass and high-pass differ in length. */
+    private final MethodHandle forwardBi, inverseBi;
     private final MemorySegment ctx;
 
     /** Loads {@code libvectorwave_amd.so} from {@code libraryPath} and creates a context on {@code device}. */
@@ -57,6 +59,16 @@ public final class AmdFfm implements AutoCloseable {
         inverse = fn("vw_modwt_inverse_f64", FunctionDescriptor.of(JAVA_INT, ADDRESS, ADDRESS, ADDRESS, JAVA_LONG,
                 JAVA_LONG, ADDRESS, ADDRESS, JAVA_INT, JAVA_INT, JAVA_INT, JAVA_INT, JAVA_INT, JAVA_INT, JAVA_INT,
                 ADDRESS));
+        // biorthogonal banks: vw_modwt_forward_bi_f64(ctx, x, B, N, ldx, lo, Llo, hi, Lhi, wavelet_id, boundary, J,
+        //                                             flags, details, approx)
+        forwardBi = fn("vw_modwt_forward_bi_f64", FunctionDescriptor.of(JAVA_INT, ADDRESS, ADDRESS, JAVA_LONG, JAVA_LONG,
+                JAVA_LONG, ADDRESS, JAVA_INT, ADDRESS, JAVA_INT, JAVA_INT, JAVA_INT, JAVA_INT, JAVA_INT, ADDRESS,
+                ADDRESS));
+        // vw_modwt_inverse_bi_f64(ctx, details, approx, B, N, lo, Llo, hi, Lhi, wavelet_id, boundary, J, detail_mask,
+        //                         approx_zero, flags, y)
+        inverseBi = fn("vw_modwt_inverse_bi_f64", FunctionDescriptor.of(JAVA_INT, ADDRESS, ADDRESS, ADDRESS, JAVA_LONG,
+                JAVA_LONG, ADDRESS, JAVA_INT, ADDRESS, JAVA_INT, JAVA_INT, JAVA_INT, JAVA_INT, JAVA_INT, JAVA_INT,
+                JAVA_INT, ADDRESS));
         // vw_swt_denoise_f64(ctx, x, B, N, ldx, lo, hi, L, wavelet_id, boundary, J, threshold, soft, flags, y, thr)
         denoise = fn("vw_swt_denoise_f64", FunctionDescriptor.of(JAVA_INT, ADDRESS, ADDRESS, JAVA_LONG, JAVA_LONG,
                 JAVA_LONG, ADDRESS, ADDRESS, JAVA_INT, JAVA_INT, JAVA_INT, JAVA_INT, ValueLayout.JAVA_DOUBLE, JAVA_INT,

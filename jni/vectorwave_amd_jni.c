@@ -122,6 +122,20 @@ static int get_taps(JNIEnv *e, jdoubleArray lo, jdoubleArray hi, Taps *tl, Taps 
   return 1;
 }
 
+/* A biorthogonal bank (BiorthogonalSpline / ReverseBiorthogonalSpline): 1..64 taps each, the two lengths free. */
+static int get_taps_bi(JNIEnv *e, jdoubleArray lo, jdoubleArray hi, Taps *tl, Taps *th) {
+  if (!lo || !hi) { null_error(e, "filter taps cannot be null"); return 0; }
+  tl->n = (*e)->GetArrayLength(e, lo);
+  th->n = (*e)->GetArrayLength(e, hi);
+  if (tl->n < 1 || tl->n > 64 || th->n < 1 || th->n > 64) {
+    arg_error(e, "filter taps must be 1..64 values each");
+    return 0;
+  }
+  (*e)->GetDoubleArrayRegion(e, lo, 0, tl->n, tl->v);
+  (*e)->GetDoubleArrayRegion(e, hi, 0, th->n, th->v);
+  return 1;
+}
+
 static size_t alen(JNIEnv *e, jdoubleArray a) { return a ? (size_t)(*e)->GetArrayLength(e, a) : 0; }
 
 static int flat_ok(JNIEnv *e, jint B, jint N) {
@@ -455,12 +469,11 @@ static jsize row_len(JNIEnv *e, jobjectArray rows) {
   return n;
 }
 
-JNIEXPORT jint JNICALL VW_JNI(modwtForwardAoS)(JNIEnv *e, jclass c, jlong ctx, jobjectArray x, jdoubleArray lo,
-                                               jdoubleArray hi, jint wid, jint boundary, jint J, jint flags,
-                                               jobjectArray details, jobjectArray approx) {
-  (void)c;
+/* bi: lo and hi may differ in length (the analysis pair of a biorthogonal bank, vw_modwt_forward_bi_f64) */
+static jint aos_forward(JNIEnv *e, jlong ctx, jobjectArray x, jdoubleArray lo, jdoubleArray hi, jint wid,
+                        jint boundary, jint J, jint flags, jobjectArray details, jobjectArray approx, int bi) {
   Taps tl, th;
-  if (!get_taps(e, lo, hi, &tl, &th)) return VW_ERR_ARG;
+  if (!(bi ? get_taps_bi(e, lo, hi, &tl, &th) : get_taps(e, lo, hi, &tl, &th))) return VW_ERR_ARG;
   if (J < 1) return arg_error(e, "levels must be >= 1");
   const jsize N = row_len(e, x);
   if (N < 1) return VW_ERR_ARG;
@@ -478,8 +491,10 @@ JNIEXPORT jint JNICALL VW_JNI(modwtForwardAoS)(JNIEnv *e, jclass c, jlong ctx, j
     const jsize nb = B - b0 < CB ? B - b0 : CB;
     if (!gather_rows(e, x, b0, nb, N, px)) { st = VW_ERR_ARG; break; }
     vw_set_signal_base(b0);
-    st = vw_modwt_forward_f64(CTX(ctx), px, nb, N, N, tl.v, th.v, tl.n, wid, boundary, J,
-                              (unsigned)flags | HOST_FLAGS, pd, pa);
+    st = bi ? vw_modwt_forward_bi_f64(CTX(ctx), px, nb, N, N, tl.v, tl.n, th.v, th.n, wid, boundary, J,
+                                      (unsigned)flags | HOST_FLAGS, pd, pa)
+            : vw_modwt_forward_f64(CTX(ctx), px, nb, N, N, tl.v, th.v, tl.n, wid, boundary, J,
+                                   (unsigned)flags | HOST_FLAGS, pd, pa);
     vw_set_signal_base(0);
     for (jsize l = 0; l < J && st == VW_OK; ++l) {
       jobjectArray pl = plane(e, details, l);
@@ -492,12 +507,27 @@ JNIEXPORT jint JNICALL VW_JNI(modwtForwardAoS)(JNIEnv *e, jclass c, jlong ctx, j
   return st;
 }
 
-JNIEXPORT jint JNICALL VW_JNI(modwtInverseAoS)(JNIEnv *e, jclass c, jlong ctx, jobjectArray details,
-                                               jobjectArray approx, jdoubleArray lo, jdoubleArray hi, jint wid,
-                                               jint boundary, jint flags, jobjectArray y) {
+JNIEXPORT jint JNICALL VW_JNI(modwtForwardAoS)(JNIEnv *e, jclass c, jlong ctx, jobjectArray x, jdoubleArray lo,
+                                               jdoubleArray hi, jint wid, jint boundary, jint J, jint flags,
+                                               jobjectArray details, jobjectArray approx) {
   (void)c;
+  return aos_forward(e, ctx, x, lo, hi, wid, boundary, J, flags, details, approx, 0);
+}
+
+/* BiorthogonalSpline / ReverseBiorthogonalSpline: lo = lowPassDecomposition(), hi = highPassDecomposition(), of
+ * different lengths.  Same row chunks and signal base as modwtForwardAoS. */
+JNIEXPORT jint JNICALL VW_JNI(modwtForwardBiAoS)(JNIEnv *e, jclass c, jlong ctx, jobjectArray x, jdoubleArray lo,
+                                                 jdoubleArray hi, jint wid, jint boundary, jint J, jint flags,
+                                                 jobjectArray details, jobjectArray approx) {
+  (void)c;
+  return aos_forward(e, ctx, x, lo, hi, wid, boundary, J, flags, details, approx, 1);
+}
+
+/* bi: the synthesis pair of a biorthogonal bank (vw_modwt_inverse_bi_f64) */
+static jint aos_inverse(JNIEnv *e, jlong ctx, jobjectArray details, jobjectArray approx, jdoubleArray lo,
+                        jdoubleArray hi, jint wid, jint boundary, jint flags, jobjectArray y, int bi) {
   Taps tl, th;
-  if (!get_taps(e, lo, hi, &tl, &th)) return VW_ERR_ARG;
+  if (!(bi ? get_taps_bi(e, lo, hi, &tl, &th) : get_taps(e, lo, hi, &tl, &th))) return VW_ERR_ARG;
   if (!details) return null_error(e, "detailPerLevel cannot be null");
   const jsize J = (*e)->GetArrayLength(e, details);
   if (J < 1) return arg_error(e, "levels must be > 0");
@@ -521,13 +551,30 @@ JNIEXPORT jint JNICALL VW_JNI(modwtInverseAoS)(JNIEnv *e, jclass c, jlong ctx, j
     if (st != VW_OK) break;
     if (!gather_rows(e, approx, b0, nb, N, pa)) { st = VW_ERR_ARG; break; }
     vw_set_signal_base(b0);
-    st = vw_modwt_inverse_f64(CTX(ctx), pd, pa, nb, N, tl.v, th.v, tl.n, wid, boundary, J, 0xFFFFFFFFu, 0,
-                              (unsigned)flags | HOST_FLAGS, py);
+    st = bi ? vw_modwt_inverse_bi_f64(CTX(ctx), pd, pa, nb, N, tl.v, tl.n, th.v, th.n, wid, boundary, J, 0xFFFFFFFFu,
+                                      0, (unsigned)flags | HOST_FLAGS, py)
+            : vw_modwt_inverse_f64(CTX(ctx), pd, pa, nb, N, tl.v, th.v, tl.n, wid, boundary, J, 0xFFFFFFFFu, 0,
+                                   (unsigned)flags | HOST_FLAGS, py);
     vw_set_signal_base(0);
     if (st == VW_OK && !scatter_rows(e, y, b0, nb, N, py)) st = VW_ERR_ARG;
   }
   trim_slots();
   return st;
+}
+
+JNIEXPORT jint JNICALL VW_JNI(modwtInverseAoS)(JNIEnv *e, jclass c, jlong ctx, jobjectArray details,
+                                               jobjectArray approx, jdoubleArray lo, jdoubleArray hi, jint wid,
+                                               jint boundary, jint flags, jobjectArray y) {
+  (void)c;
+  return aos_inverse(e, ctx, details, approx, lo, hi, wid, boundary, flags, y, 0);
+}
+
+/* lo = lowPassReconstruction(), hi = highPassReconstruction() of a biorthogonal bank */
+JNIEXPORT jint JNICALL VW_JNI(modwtInverseBiAoS)(JNIEnv *e, jclass c, jlong ctx, jobjectArray details,
+                                                 jobjectArray approx, jdoubleArray lo, jdoubleArray hi, jint wid,
+                                                 jint boundary, jint flags, jobjectArray y) {
+  (void)c;
+  return aos_inverse(e, ctx, details, approx, lo, hi, wid, boundary, flags, y, 1);
 }
 
 JNIEXPORT jint JNICALL VW_JNI(swtDenoiseAoS)(JNIEnv *e, jclass c, jlong ctx, jobjectArray x, jdoubleArray lo,

@@ -10,9 +10,11 @@ include/vectorwave_amd.h).  This package is the host-side mirror of the referenc
   FinancialAnalyzer, FinancialWaveletAnalyzer and their configs (com.morphiqlabs.financial)
   MODWTStreamingTransform, MultiLevelMODWTStreamingTransform  (core/modwt/streaming)
   BatchMODWT, BatchStreamingMODWT                             (ext/extensions/modwt)
-  Haar, Daubechies, Symlet, Coiflet                           (core/api wavelets)
+  Haar, Daubechies, Symlet, Coiflet, BiorthogonalSpline,
+  ReverseBiorthogonalSpline                                   (core/api wavelets)
 """
-from .wavelets import Coiflet, Daubechies, Haar, Symlet, Wavelet, available_wavelets, get_wavelet
+from .wavelets import (BiorthogonalSpline, BiorthogonalWavelet, Coiflet, Daubechies, Haar, ReverseBiorthogonalSpline,
+                       Symlet, Wavelet, available_wavelets, get_wavelet)
 from .errors import (ErrorCode, InvalidArgumentException, InvalidSignalException, InvalidStateException,
                      WaveletTransformException)
 from .modwt import (BoundaryMode, MODWTResult, MODWTTransform, MultiLevelMODWTResult, MultiLevelMODWTTransform,
@@ -36,5 +38,5 @@ __all__ = [
     "MODWTStreamingTransformImpl", "MultiLevelMODWTStreamingTransform",
     "BatchStreamingMODWT", "Engine", "max_levels", "version", "DeviceGroup",
     "FinancialAnalysisConfig", "FinancialAnalyzer", "FinancialConfig", "FinancialWaveletAnalyzer",
-    "VolatilityClassification",
+    "VolatilityClassification", "BiorthogonalSpline", "BiorthogonalWavelet", "ReverseBiorthogonalSpline",
 ]

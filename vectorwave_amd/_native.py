@@ -67,6 +67,19 @@ SIGNATURES = {
                                       c_void_p, c_void_p]),
     "vw_modwt1_inverse_f64": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int64, _dp, _dp, c_int, c_int, c_uint,
                                       c_void_p]),
+    # biorthogonal banks: (lo, Llo, hi, Lhi)
+    "vw_modwt_forward_bi_f64": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int64, _dp, c_int, _dp, c_int, c_int,
+                                        c_int, c_int, c_uint, c_void_p, c_void_p]),
+    "vw_modwt_forward_bi_f32": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int64, _dp, c_int, _dp, c_int, c_int,
+                                        c_int, c_int, c_uint, c_void_p, c_void_p]),
+    "vw_modwt_inverse_bi_f64": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int64, _dp, c_int, _dp, c_int, c_int,
+                                        c_int, c_int, c_uint, c_int, c_uint, c_void_p]),
+    "vw_modwt_inverse_bi_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int64, _dp, c_int, _dp, c_int, c_int,
+                                        c_int, c_int, c_uint, c_int, c_uint, c_void_p]),
+    "vw_modwt1_forward_bi_f64": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int64, _dp, c_int, _dp, c_int, c_int,
+                                         c_uint, c_void_p, c_void_p]),
+    "vw_modwt1_inverse_bi_f64": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int64, _dp, c_int, _dp, c_int, c_int,
+                                         c_uint, c_void_p]),
     "vw_modwt_energy_f64": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int64, _dp, _dp, c_int, c_int, c_int,
                                     c_int, c_uint, c_void_p]),
     "vw_energy_planes_f64": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int, c_uint, c_void_p]),

@@ -15,7 +15,7 @@ from . import _native as nat
 from .engine import Engine, _check, _is_device_tensor
 from .errors import InvalidArgumentException
 from .modwt import BoundaryMode, _check_boundary, _engine_for, relative_energy
-from .wavelets import Haar, Wavelet
+from .wavelets import Haar, Wavelet, require_orthogonal
 
 try:
     import torch
@@ -46,7 +46,7 @@ def _check_batch_reach(wavelet: Wavelet, n: int, levels: int) -> None:
     """BatchSIMDMODWT.generalBatchMODWTSoAWithScaledFilters (:384-424) indexes (t - l + N) % N: with an
     upsampled filter longer than N + 1 that index goes negative and Java throws
     ArrayIndexOutOfBoundsException at the first such level (IndexError here, before any work)."""
-    L = len(wavelet.lowPassDecomposition())
+    L = len(wavelet.lowPassDecomposition())  # :397: the loop bound is scaledLow.length for both filters
     for j in range(1, levels + 1):
         Lj = (L - 1) * (1 << (j - 1)) + 1
         if Lj > n + 1:
@@ -100,6 +100,7 @@ class BatchMODWT:
         fused with the forward where its cascade fits."""
         if levels < 1:
             raise InvalidArgumentException("levels must be >= 1")
+        require_orthogonal(wavelet, "BatchMODWT.energyBatch")
         x = _validate_aos(signals)
         _check_batch_reach(wavelet, x.shape[1], levels)
         flags = nat.FLAG_REF_NONFINITE | (nat.FLAG_FMA if fma else 0)
@@ -223,6 +224,7 @@ class BatchStreamingMODWT:
         if levels < 1:
             raise InvalidArgumentException("levels must be >= 1")
         _check_boundary(boundaryMode)
+        require_orthogonal(wavelet, "BatchStreamingMODWT")
         self.wavelet = wavelet
         self.boundaryMode = BoundaryMode(boundaryMode)
         self.levels = levels

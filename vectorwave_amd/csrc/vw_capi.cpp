@@ -749,12 +749,36 @@ static vw_status check_levels(int64_t N, int L, int J, unsigned flags) {
   return VW_OK;
 }
 
+// The _bi_ entry points (two filter lengths; Lhi == 0: an equal-length entry point, nothing to check).  L has
+// passed check_common / check_levels, which for CORE_LEVELS is the reference's cap on the low-pass length alone
+// (calculateMaxLevels :455-501); its guards then want both upsampled filters within the signal (:717-729,
+// :561-574).  Without CORE_LEVELS the longer filter meets the equal-length call's checks.
+static vw_status check_bank(int64_t N, int L, int Lhi, int J, unsigned flags, bool forward) {
+  if (Lhi == 0) return VW_OK;
+  if (Lhi < 1 || Lhi > kMaxTaps) return fail(VW_ERR_ARG, "filter length %d unsupported (1..%d)", Lhi, kMaxTaps);
+  if (flags & VW_FLAG_CORE_LEVELS) {
+    if (vw_upsampled_length(std::max(L, Lhi), J) > N)
+      return fail(VW_ERR_TOO_LARGE, "Upsampled %s filter length exceeds signal length", forward ? "analysis" : "reconstruction");
+  } else if (forward && Lhi > L) {
+    if (vw_upsampled_length(Lhi, J) > (int64_t)1 << 30) return fail(VW_ERR_TOO_LARGE, "upsampled filter too long");
+  }
+  return VW_OK;
+}
+
 template <typename T>
 static void copy_taps(T* dst, const double* src, int L) {
   // base taps * (1.0 / Math.sqrt(2.0)) in double, then rounded to T  (ScalarOps.java:911-914)
   const double s = 1.0 / std::sqrt(2.0);
   for (int i = 0; i < L; ++i) dst[i] = (T)(src[i] * s);
   for (int i = L; i < kMaxTaps; ++i) dst[i] = T(0);
+}
+
+// Both filters of a call for a kernel of `taps` taps (the plan's, vw_plan.h): a bank of two lengths has its shorter
+// filter zero-extended, and on the pairwise inverses (taps = k.L) a longer high-pass truncated.
+template <typename T, typename Call>
+static void copy_bank(T* lo, T* hi, const Call& k, int taps, int taps_hi = 0) {
+  copy_taps(lo, k.lo, std::min(k.L, taps));
+  copy_taps(hi, k.hi, std::min(k.Lhi > 0 ? k.Lhi : k.L, taps_hi > 0 ? taps_hi : taps));
 }
 
 // Calls that synchronize cannot be recorded into a graph (vw_capture_begin).
@@ -861,16 +885,14 @@ static vw_status forward_steps(vw_ctx* c, const FwdCall<T>& k, const FwdPlan<T>&
       d.src = src; d.out = dst;
       d.nf_flag = s.probe ? c->nf : nullptr;
       for (int g = 0; g < d.g; ++g) d.out_d[g] = det + (size_t)g * plane;
-      copy_taps(d.lo, k.lo, k.L);
-      copy_taps(d.hi, k.hi, k.L);
+      copy_bank(d.lo, d.hi, k, d.taps);
       LaunchTimer lt(c, "forward_level");
       e = launch_deep<T>(d, s.lds, p.fma, false, c->stream);
     } else if (s.kind == kStepMulti) {
       MultiArgs<T> m = s.multi;
       m.src_a = src; m.out_a = dst;
       for (int g = 0; g < m.nlev; ++g) m.out_d[g] = det + (size_t)g * plane;
-      copy_taps(m.lo, k.lo, k.L);
-      copy_taps(m.hi, k.hi, k.L);
+      copy_bank(m.lo, m.hi, k, m.taps);
       LaunchTimer lt(c, "forward_level");
       e = launch_forward_multi<T>(m, s.lds, p.fma, c->stream);
     } else {
@@ -878,8 +900,7 @@ static vw_status forward_steps(vw_ctx* c, const FwdCall<T>& k, const FwdPlan<T>&
       a.src_a = src; a.out_a = dst; a.out_d = det;
       a.hist = k.hist ? k.hist[s.jlo - 1] : nullptr;
       a.bad = c->bad;
-      copy_taps(a.lo, k.lo, k.L);
-      copy_taps(a.hi, k.hi, k.L);
+      copy_bank(a.lo, a.hi, k, a.taps);
       LaunchTimer lt(c, "forward_level");
       e = s.kind == kStepSweep ? launch_forward_sweep<T>(a, p.fma, c->stream)
                                : launch_forward_level<T>(a, s.lds, p.fma, c->stream);
@@ -916,8 +937,7 @@ static vw_status forward_impl(vw_ctx* c, FwdCall<T> k) {
     a.bad = c->bad;
     a.nf_flag = p.nf_probed ? c->nf : nullptr;
     for (int j = 0; j < k.J; ++j) a.hist[j] = k.hist ? k.hist[j] : nullptr;
-    copy_taps(a.lo, k.lo, k.L);
-    copy_taps(a.hi, k.hi, k.L);
+    copy_bank(a.lo, a.hi, k, a.taps, a.taps_hi);
     LaunchTimer lt(c, "forward");
     hipError_t e = p.kernel == kFwdMfma    ? mfma_forward(a, p.lds, c->stream)
                  : p.kernel == kFwdBlk     ? launch_forward_blk<T>(a, p.threads, p.lds, p.fma, p.nv, c->stream)
@@ -943,8 +963,8 @@ static vw_status forward_impl(vw_ctx* c, FwdCall<T> k) {
         r.hist_new[j] = k.hist_update ? k.hist[j] : nullptr;
       }
     }
-    copy_taps(r.lo, k.lo, k.L);
-    copy_taps(r.hi, k.hi, k.L);
+    r.Lhi = k.Lhi;
+    copy_bank(r.lo, r.hi, k, p.args.taps, p.args.taps_hi);
     VW_TRY(ref_nonfinite<T>(c, planes, r, false, p.nf_probed, p.res.ref_grid));
   }
   if (p.validate) {
@@ -974,8 +994,7 @@ static vw_status inverse_steps(vw_ctx* c, const InvCall<T>& k, const InvPlan<T>&
         d.src_d[g] = det(s.jlo + g, p.args.lv[s.jlo - 1 + g].use_d);
         d.thr[g] = thr(s.jlo + g);
       }
-      copy_taps(d.lo, k.lo, k.L);
-      copy_taps(d.hi, k.hi, k.L);
+      copy_bank(d.lo, d.hi, k, d.taps);
       LaunchTimer lt(c, "inverse_level");
       e = launch_deep<T>(d, s.lds, p.fma, true, c->stream);
     } else if (s.kind == kStepMulti) {
@@ -986,8 +1005,7 @@ static vw_status inverse_steps(vw_ctx* c, const InvCall<T>& k, const InvPlan<T>&
         m.src_d[g] = det(s.jlo + g, p.args.lv[s.jlo - 1 + g].use_d);
         m.thr[g] = thr(s.jlo + g);
       }
-      copy_taps(m.lo, k.lo, k.L);
-      copy_taps(m.hi, k.hi, k.L);
+      copy_bank(m.lo, m.hi, k, m.taps);
       LaunchTimer lt(c, "inverse_level");
       e = launch_inverse_multi<T>(m, s.lds, p.fma, c->stream);
     } else {
@@ -1003,8 +1021,7 @@ static vw_status inverse_steps(vw_ctx* c, const InvCall<T>& k, const InvPlan<T>&
           a.thr3 = thr(s.jhi - 2);
         }
       }
-      copy_taps(a.lo, k.lo, k.L);
-      copy_taps(a.hi, k.hi, k.L);
+      copy_bank(a.lo, a.hi, k, a.taps);
       LaunchTimer lt(c, "inverse_level");
       e = s.kind == kStepSweepG ? launch_inverse_sweepg<T>(a, s.G, s.ka, s.R, p.fma, c->stream)
         : s.kind == kStepSweep  ? launch_inverse_sweep<T>(a, p.fma, c->stream)
@@ -1028,8 +1045,7 @@ static vw_status inverse_impl(vw_ctx* c, InvCall<T> k) {
     InvArgs<T> a = p.args;
     a.details = k.details; a.approx = k.approx; a.y = k.y; a.thr = k.thr;
     a.nf_flag = p.nf_probed ? c->nf : nullptr;
-    copy_taps(a.lo, k.lo, k.L);
-    copy_taps(a.hi, k.hi, k.L);
+    copy_bank(a.lo, a.hi, k, a.taps, a.taps_hi);
     LaunchTimer lt(c, "inverse");
     hipError_t e = p.kernel == kInvMfma ? mfma_inverse(a, p.lds, c->stream)
                                         : launch_inverse_fused<T>(a, p.threads, p.lds, p.fma, p.nv, c->stream);
@@ -1045,8 +1061,8 @@ static vw_status inverse_impl(vw_ctx* c, InvCall<T> k) {
     r.x = k.approx_zero ? nullptr : k.approx; r.det_in = k.details; r.y = k.y;
     r.thr = k.thr; r.thr_ld = k.thr_ld; r.soft = k.soft;
     r.B = k.B; r.N = (int)k.N; r.J = k.J; r.L = k.L; r.mode = ref_mode(k.boundary);
-    copy_taps(r.lo, k.lo, k.L);
-    copy_taps(r.hi, k.hi, k.L);
+    r.Lhi = k.Lhi;
+    copy_bank(r.lo, r.hi, k, p.args.taps, p.args.taps_hi);
     for (int j = 0; j < k.J; ++j) r.lv[j] = p.args.lv[j];
     VW_TRY(ref_nonfinite<T>(c, planes, r, true, p.nf_probed, p.res.ref_grid));
   }
@@ -1145,7 +1161,7 @@ struct Staging {
 template <typename T>
 static vw_status forward_host(vw_ctx* c, const T* x, int64_t B, int64_t N, int64_t ldx, const double* lo,
                               const double* hi, int L, int boundary, int J, unsigned flags, T* details,
-                              int64_t det_stride, T* approx) {
+                              int64_t det_stride, T* approx, int Lhi = 0) {
   if (c->capturing) return fail(VW_ERR_STATE, "host-memory calls cannot be captured (they synchronize)");
   Staging s(c);
   T *dx, *dd, *da;
@@ -1154,7 +1170,7 @@ static vw_status forward_host(vw_ctx* c, const T* x, int64_t B, int64_t N, int64
   VW_TRY(s.in<T>(nullptr, (size_t)B * N, &da));
   FwdCall<T> fk;
   fk.x = dx; fk.B = B; fk.N = N; fk.ldx = ldx; fk.lo = lo; fk.hi = hi; fk.L = L; fk.boundary = boundary; fk.J = J;
-  fk.flags = flags & ~(VW_FLAG_SYNC | VW_FLAG_HOST_MEMORY); fk.details = dd; fk.approx = da;
+  fk.flags = flags & ~(VW_FLAG_SYNC | VW_FLAG_HOST_MEMORY); fk.details = dd; fk.approx = da; fk.Lhi = Lhi;
   VW_TRY(forward_impl<T>(c, fk));
   VW_TRY(s.out_planes(details, dd, (size_t)J, (size_t)(B * N), (size_t)det_stride));
   VW_TRY(s.out(approx, da, (size_t)B * N));
@@ -1165,7 +1181,7 @@ static vw_status forward_host(vw_ctx* c, const T* x, int64_t B, int64_t N, int64
 template <typename T>
 static vw_status inverse_host(vw_ctx* c, const T* details, int64_t det_stride, const T* approx, int64_t B, int64_t N,
                               const double* lo, const double* hi, int L, int wid, int boundary, int J,
-                              unsigned detail_mask, int approx_zero, unsigned flags, T* y) {
+                              unsigned detail_mask, int approx_zero, unsigned flags, T* y, int Lhi = 0) {
   if (c->capturing) return fail(VW_ERR_STATE, "host-memory calls cannot be captured (they synchronize)");
   Staging s(c);
   T *dd = nullptr, *da = nullptr, *dy;
@@ -1175,7 +1191,7 @@ static vw_status inverse_host(vw_ctx* c, const T* details, int64_t det_stride, c
   InvCall<T> ik;
   ik.details = dd; ik.approx = da; ik.B = B; ik.N = N; ik.lo = lo; ik.hi = hi; ik.L = L; ik.wid = wid;
   ik.boundary = boundary; ik.J = J; ik.detail_mask = detail_mask; ik.approx_zero = approx_zero;
-  ik.flags = flags & ~(VW_FLAG_SYNC | VW_FLAG_HOST_MEMORY); ik.y = dy;
+  ik.flags = flags & ~(VW_FLAG_SYNC | VW_FLAG_HOST_MEMORY); ik.y = dy; ik.Lhi = Lhi;
   VW_TRY(inverse_impl<T>(c, ik));
   VW_TRY(s.out(y, dy, (size_t)B * N));
   VW_HIP(hipStreamSynchronize(c->stream));
@@ -1185,21 +1201,22 @@ static vw_status inverse_host(vw_ctx* c, const T* details, int64_t det_stride, c
 template <typename T>
 static vw_status modwt_forward(vw_ctx* c, const T* x, int64_t B, int64_t N, int64_t ldx, const double* lo,
                                const double* hi, int L, int wid, int boundary, int J, unsigned flags, T* details,
-                               T* approx) {
+                               T* approx, int Lhi = 0) {
   (void)wid;
   VW_TRY(check_common(c, x, details, lo, hi, B, N, L, boundary));
   if (!approx) return fail(VW_ERR_NULL, "approx is null");
   if (ldx < N) return fail(VW_ERR_ARG, "ldx (%lld) < N (%lld)", (long long)ldx, (long long)N);
   VW_TRY(check_levels(N, L, J, flags));
+  VW_TRY(check_bank(N, L, Lhi, J, flags, true));
   std::lock_guard<std::recursive_mutex> g(c->mu);
   hipSetDevice(c->device);
   if (flags & VW_FLAG_HOST_MEMORY) {
-    VW_TRY(forward_host<T>(c, x, B, N, ldx, lo, hi, L, boundary, J, flags, details, B * N, approx));
+    VW_TRY(forward_host<T>(c, x, B, N, ldx, lo, hi, L, boundary, J, flags, details, B * N, approx, Lhi));
     return ok();
   }
   FwdCall<T> fk;
   fk.x = x; fk.B = B; fk.N = N; fk.ldx = ldx; fk.lo = lo; fk.hi = hi; fk.L = L; fk.boundary = boundary; fk.J = J;
-  fk.flags = flags; fk.details = details; fk.approx = approx;
+  fk.flags = flags; fk.details = details; fk.approx = approx; fk.Lhi = Lhi;
   VW_TRY(forward_impl<T>(c, fk));
   return ok();
 }
@@ -1207,7 +1224,7 @@ static vw_status modwt_forward(vw_ctx* c, const T* x, int64_t B, int64_t N, int6
 template <typename T>
 static vw_status modwt_inverse(vw_ctx* c, const T* details, const T* approx, int64_t B, int64_t N, const double* lo,
                                const double* hi, int L, int wid, int boundary, int J, unsigned detail_mask,
-                               int approx_zero, unsigned flags, T* y) {
+                               int approx_zero, unsigned flags, T* y, int Lhi = 0) {
   if (!c) return fail(VW_ERR_NULL, "ctx is null");
   if (!y || !lo || !hi) return fail(VW_ERR_NULL, "null argument");
   if (!details && detail_mask) return fail(VW_ERR_NULL, "details is null");
@@ -1218,17 +1235,18 @@ static vw_status modwt_inverse(vw_ctx* c, const T* details, const T* approx, int
   // periodic inverse (VectorWaveSwtAdapter.reconstructPeriodic :444-474) wraps instead.
   if ((flags & VW_FLAG_CORE_LEVELS) && vw_upsampled_length(L, J) > N)
     return fail(VW_ERR_TOO_LARGE, "Upsampled reconstruction filter length exceeds signal length");
+  VW_TRY(check_bank(N, L, Lhi, J, flags, false));
   std::lock_guard<std::recursive_mutex> g(c->mu);
   hipSetDevice(c->device);
   if (flags & VW_FLAG_HOST_MEMORY) {
     VW_TRY(inverse_host<T>(c, details, B * N, approx, B, N, lo, hi, L, wid, boundary, J, detail_mask, approx_zero,
-                           flags, y));
+                           flags, y, Lhi));
     return ok();
   }
   InvCall<T> ik;
   ik.details = details; ik.approx = approx; ik.B = B; ik.N = N; ik.lo = lo; ik.hi = hi; ik.L = L; ik.wid = wid;
   ik.boundary = boundary; ik.J = J; ik.detail_mask = detail_mask; ik.approx_zero = approx_zero; ik.flags = flags;
-  ik.y = y;
+  ik.y = y; ik.Lhi = Lhi;
   VW_TRY(inverse_impl<T>(c, ik));
   return ok();
 }
@@ -1254,6 +1272,42 @@ extern "C" vw_status vw_modwt_inverse_f32(vw_ctx* c, const float* details, const
                                           int J, unsigned detail_mask, int approx_zero, unsigned flags, float* y) {
   return modwt_inverse<float>(c, details, approx, B, N, lo, hi, L, wid, boundary, J, detail_mask, approx_zero, flags,
                               y);
+}
+
+// Biorthogonal banks (BiorthogonalSpline / ReverseBiorthogonalSpline): lo has Llo taps, hi has Lhi.  Equal
+// lengths are the calls above, argument for argument.
+static int bank_hi(int Llo, int Lhi) { return Lhi == Llo ? 0 : Lhi; }
+static vw_status bank_arg(int Lhi) {
+  if (Lhi < 1 || Lhi > kMaxTaps) return fail(VW_ERR_ARG, "filter length %d unsupported (1..%d)", Lhi, kMaxTaps);
+  return VW_OK;
+}
+extern "C" vw_status vw_modwt_forward_bi_f64(vw_ctx* c, const double* x, int64_t B, int64_t N, int64_t ldx,
+                                             const double* lo, int Llo, const double* hi, int Lhi, int wid,
+                                             int boundary, int J, unsigned flags, double* details, double* approx) {
+  VW_TRY(bank_arg(Lhi));
+  return modwt_forward<double>(c, x, B, N, ldx, lo, hi, Llo, wid, boundary, J, flags, details, approx, bank_hi(Llo, Lhi));
+}
+extern "C" vw_status vw_modwt_forward_bi_f32(vw_ctx* c, const float* x, int64_t B, int64_t N, int64_t ldx,
+                                             const double* lo, int Llo, const double* hi, int Lhi, int wid,
+                                             int boundary, int J, unsigned flags, float* details, float* approx) {
+  VW_TRY(bank_arg(Lhi));
+  return modwt_forward<float>(c, x, B, N, ldx, lo, hi, Llo, wid, boundary, J, flags, details, approx, bank_hi(Llo, Lhi));
+}
+extern "C" vw_status vw_modwt_inverse_bi_f64(vw_ctx* c, const double* details, const double* approx, int64_t B,
+                                             int64_t N, const double* lo, int Llo, const double* hi, int Lhi, int wid,
+                                             int boundary, int J, unsigned detail_mask, int approx_zero,
+                                             unsigned flags, double* y) {
+  VW_TRY(bank_arg(Lhi));
+  return modwt_inverse<double>(c, details, approx, B, N, lo, hi, Llo, wid, boundary, J, detail_mask, approx_zero,
+                               flags, y, bank_hi(Llo, Lhi));
+}
+extern "C" vw_status vw_modwt_inverse_bi_f32(vw_ctx* c, const float* details, const float* approx, int64_t B,
+                                             int64_t N, const double* lo, int Llo, const double* hi, int Lhi, int wid,
+                                             int boundary, int J, unsigned detail_mask, int approx_zero,
+                                             unsigned flags, float* y) {
+  VW_TRY(bank_arg(Lhi));
+  return modwt_inverse<float>(c, details, approx, B, N, lo, hi, Llo, wid, boundary, J, detail_mask, approx_zero,
+                              flags, y, bank_hi(Llo, Lhi));
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1407,15 +1461,16 @@ extern "C" vw_status vw_modwt_inverse_multi_dev_f64(vw_ctx* const* ctxs, int nct
 
 // ------------------------------------------------------------------------------------------------
 // Single level (MODWTTransform): any N >= 1 (no L <= N guard), pairwise inverse sums.
-extern "C" vw_status vw_modwt1_forward_f64(vw_ctx* c, const double* x, int64_t B, int64_t N, int64_t ldx,
-                                           const double* lo, const double* hi, int L, int boundary, unsigned flags,
-                                           double* approx, double* detail) {
+// Lhi: the high-pass length of a two-length bank (0 = L)
+static vw_status modwt1_forward(vw_ctx* c, const double* x, int64_t B, int64_t N, int64_t ldx, const double* lo,
+                                const double* hi, int L, int Lhi, int boundary, unsigned flags, double* approx,
+                                double* detail) {
   VW_TRY(check_common(c, x, detail, lo, hi, B, N, L, boundary));
   if (!approx) return fail(VW_ERR_NULL, "approx is null");
   if (ldx < N) return fail(VW_ERR_ARG, "ldx < N");
   std::lock_guard<std::recursive_mutex> g(c->mu);
   hipSetDevice(c->device);
-  const bool haar_quirk = (flags & VW_FLAG_BATCH_HAAR) && L == 2 && boundary == VW_PERIODIC;
+  const bool haar_quirk = (flags & VW_FLAG_BATCH_HAAR) && L == 2 && Lhi == 0 && boundary == VW_PERIODIC;
   auto run = [&](const double* dx, double* da, double* dd, unsigned fl) -> vw_status {
     if (haar_quirk) {
       LaunchTimer lt(c, "forward1");
@@ -1425,7 +1480,7 @@ extern "C" vw_status vw_modwt1_forward_f64(vw_ctx* c, const double* x, int64_t B
     }
     FwdCall<double> fk;
     fk.x = dx; fk.B = B; fk.N = N; fk.ldx = ldx; fk.lo = lo; fk.hi = hi; fk.L = L; fk.boundary = boundary; fk.J = 1;
-    fk.flags = fl & ~VW_FLAG_FFT_SWITCH; fk.details = dd; fk.approx = da; fk.single_level = true;
+    fk.flags = fl & ~VW_FLAG_FFT_SWITCH; fk.details = dd; fk.approx = da; fk.single_level = true; fk.Lhi = Lhi;
     return forward_impl<double>(c, fk);
   };
   if (flags & VW_FLAG_HOST_MEMORY) {
@@ -1445,9 +1500,21 @@ extern "C" vw_status vw_modwt1_forward_f64(vw_ctx* c, const double* x, int64_t B
   return ok();
 }
 
-extern "C" vw_status vw_modwt1_inverse_f64(vw_ctx* c, const double* approx, const double* detail, int64_t B,
-                                           int64_t N, const double* lo, const double* hi, int L, int boundary,
-                                           unsigned flags, double* y) {
+extern "C" vw_status vw_modwt1_forward_f64(vw_ctx* c, const double* x, int64_t B, int64_t N, int64_t ldx,
+                                           const double* lo, const double* hi, int L, int boundary, unsigned flags,
+                                           double* approx, double* detail) {
+  return modwt1_forward(c, x, B, N, ldx, lo, hi, L, 0, boundary, flags, approx, detail);
+}
+extern "C" vw_status vw_modwt1_forward_bi_f64(vw_ctx* c, const double* x, int64_t B, int64_t N, int64_t ldx,
+                                              const double* lo, int Llo, const double* hi, int Lhi, int boundary,
+                                              unsigned flags, double* approx, double* detail) {
+  VW_TRY(bank_arg(Lhi));
+  return modwt1_forward(c, x, B, N, ldx, lo, hi, Llo, bank_hi(Llo, Lhi), boundary, flags, approx, detail);
+}
+
+static vw_status modwt1_inverse(vw_ctx* c, const double* approx, const double* detail, int64_t B, int64_t N,
+                                const double* lo, const double* hi, int L, int Lhi, int boundary, unsigned flags,
+                                double* y) {
   VW_TRY(check_common(c, approx, detail, lo, hi, B, N, L, boundary));
   if (!y) return fail(VW_ERR_NULL, "y is null");
   std::lock_guard<std::recursive_mutex> g(c->mu);
@@ -1460,7 +1527,7 @@ extern "C" vw_status vw_modwt1_inverse_f64(vw_ctx* c, const double* approx, cons
     VW_TRY(s.in<double>(nullptr, (size_t)B * N, &dy));
     InvCall<double> ik;
     ik.details = dd; ik.approx = da; ik.B = B; ik.N = N; ik.lo = lo; ik.hi = hi; ik.L = L; ik.boundary = boundary;
-    ik.J = 1; ik.detail_mask = 1u; ik.flags = flags & ~VW_FLAG_SYNC; ik.y = dy; ik.single_level = true;
+    ik.J = 1; ik.detail_mask = 1u; ik.flags = flags & ~VW_FLAG_SYNC; ik.y = dy; ik.single_level = true; ik.Lhi = Lhi;
     VW_TRY(inverse_impl<double>(c, ik));
     VW_TRY(s.out(y, dy, (size_t)B * N));
     VW_HIP(hipStreamSynchronize(c->stream));
@@ -1469,8 +1536,21 @@ extern "C" vw_status vw_modwt1_inverse_f64(vw_ctx* c, const double* approx, cons
   InvCall<double> ik;
   ik.details = detail; ik.approx = approx; ik.B = B; ik.N = N; ik.lo = lo; ik.hi = hi; ik.L = L;
   ik.boundary = boundary; ik.J = 1; ik.detail_mask = 1u; ik.flags = flags; ik.y = y; ik.single_level = true;
+  ik.Lhi = Lhi;
   VW_TRY(inverse_impl<double>(c, ik));
   return ok();
+}
+
+extern "C" vw_status vw_modwt1_inverse_f64(vw_ctx* c, const double* approx, const double* detail, int64_t B,
+                                           int64_t N, const double* lo, const double* hi, int L, int boundary,
+                                           unsigned flags, double* y) {
+  return modwt1_inverse(c, approx, detail, B, N, lo, hi, L, 0, boundary, flags, y);
+}
+extern "C" vw_status vw_modwt1_inverse_bi_f64(vw_ctx* c, const double* approx, const double* detail, int64_t B,
+                                              int64_t N, const double* lo, int Llo, const double* hi, int Lhi,
+                                              int boundary, unsigned flags, double* y) {
+  VW_TRY(bank_arg(Lhi));
+  return modwt1_inverse(c, approx, detail, B, N, lo, hi, Llo, bank_hi(Llo, Lhi), boundary, flags, y);
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -188,14 +188,17 @@ __device__ __forceinline__ void static_for(F&& f) {
 
 // Forward: one 16-byte vector of consecutive outputs t0..t0+V-1, both filters from one set of
 // LDS reads.  acc_e (+)= x[t0 + e - i*s] * f[i], i ascending (ScalarOps.java:707-719 order).
-template <typename T, int L, bool FMA, int S>
+// LH: the high-pass tap count of a two-length bank (VW_BI): tap position i feeds the low sum only while i < L and
+// the high sum only while i < LH (compile-time after unrolling: the short filter spends nothing on absent taps).
+template <typename T, int L, bool FMA, int S, int LH = L>
 __device__ __forceinline__ void fwd_window(const T* buf, int t0, const T* lo, const T* hi,
                                            T (&al)[VT<T>::V], T (&ah)[VT<T>::V]) {
   constexpr int V = VT<T>::V;
   using vec = typename VT<T>::v;
-  static_for<0, (L + kWinTaps - 1) / kWinTaps>([&](auto c) __attribute__((always_inline)) {
+  constexpr int LM = L > LH ? L : LH;
+  static_for<0, (LM + kWinTaps - 1) / kWinTaps>([&](auto c) __attribute__((always_inline)) {
     constexpr int I0 = decltype(c)::value * kWinTaps;
-    constexpr int I1 = (I0 + kWinTaps < L) ? I0 + kWinTaps : L;
+    constexpr int I1 = (I0 + kWinTaps < LM) ? I0 + kWinTaps : LM;
     constexpr int A = floor_div(-(I1 - 1) * S, V) * V;       // offsets e - i*S, aligned down
     constexpr int E = (floor_div(V - 1 - I0 * S, V) + 1) * V;
     constexpr int NE = E - A;
@@ -208,18 +211,21 @@ __device__ __forceinline__ void fwd_window(const T* buf, int t0, const T* lo, co
     }
     T fl[I1 - I0], fh[I1 - I0];
 #pragma unroll
-    for (int i = I0; i < I1; ++i) { fl[i - I0] = lo[i]; fh[i - I0] = hi[i]; }
+    for (int i = I0; i < I1; ++i) {
+      if (i < L) fl[i - I0] = lo[i];
+      if (i < LH) fh[i - I0] = hi[i];
+    }
 #pragma unroll
     for (int i = I0; i < I1; ++i) {
-      vmadd<FMA, kPkFwd>(al, &w[-i * S - A], fl[i - I0]);
-      vmadd<FMA, kPkFwd>(ah, &w[-i * S - A], fh[i - I0]);
+      if (i < L) vmadd<FMA, kPkFwd>(al, &w[-i * S - A], fl[i - I0]);
+      if (i < LH) vmadd<FMA, kPkFwd>(ah, &w[-i * S - A], fh[i - I0]);
     }
   });
 }
 
 template <typename T, int L, bool FMA>
 __device__ __forceinline__ void fwd_vec(const T* buf, int t0, int S, const T* lo, const T* hi, int taps,
-                                        T (&al)[VT<T>::V], T (&ah)[VT<T>::V]) {
+                                        T (&al)[VT<T>::V], T (&ah)[VT<T>::V], int taps_hi = -1) {
   constexpr int V = VT<T>::V;
   using vec = typename VT<T>::v;
   if constexpr (L > 0) {
@@ -234,7 +240,10 @@ __device__ __forceinline__ void fwd_vec(const T* buf, int t0, int S, const T* lo
       vmadd<FMA, kPkFwd>(ah, v, hi[i]);
     }
   } else {
-    for (int i = 0; i < taps; ++i) {
+    // runtime taps; a two-length bank (taps_hi >= 0, != taps): the common taps from one read, then the longer
+    // filter's remaining taps alone -- each sum still in ascending tap order
+    const int th = taps_hi < 0 ? taps : taps_hi, both = taps < th ? taps : th;
+    for (int i = 0; i < both; ++i) {
       const T fl = lo[i], fh = hi[i];
 #pragma unroll
       for (int e = 0; e < V; ++e) {
@@ -242,6 +251,16 @@ __device__ __forceinline__ void fwd_vec(const T* buf, int t0, int S, const T* lo
         al[e] = madd<FMA>(al[e], xv, fl);
         ah[e] = madd<FMA>(ah[e], xv, fh);
       }
+    }
+    for (int i = both; i < taps; ++i) {
+      const T fl = lo[i];
+#pragma unroll
+      for (int e = 0; e < V; ++e) al[e] = madd<FMA>(al[e], buf[t0 + e - i * S], fl);
+    }
+    for (int i = both; i < th; ++i) {
+      const T fh = hi[i];
+#pragma unroll
+      for (int e = 0; e < V; ++e) ah[e] = madd<FMA>(ah[e], buf[t0 + e - i * S], fh);
     }
   }
 }
@@ -604,28 +623,29 @@ __device__ __forceinline__ void regs_to_level(T* buf, const T (&r)[NV][VT<T>::V]
 // ---- Row compute: one level's convolution over the thread's NV vectors -------------------------
 // Forward, both filters from one set of LDS reads; emit(k, w, al, ah) consumes each output vector.
 // SC: 1 / 2 = register window for spacing 1 / 2 (the latter fp32 only), 0 = strided b128 reads.
-template <typename T, int L, bool FMA, int NV, int SC, bool FULL = false, typename Emit>
+template <typename T, int L, bool FMA, int NV, int SC, bool FULL = false, int LH = L, typename Emit>
 __device__ __forceinline__ void fwd_row_t(const T* buf, int nvec, int s, const T* lo, const T* hi, int taps,
-                                          Emit&& emit) {
+                                          Emit&& emit, int taps_hi = -1) {
   constexpr int V = VT<T>::V;
   using vec = typename VT<T>::v;
+  constexpr int LM = L > LH ? L : LH;
   for_vecs<L, NV, FULL>(nvec, [&](int k, int w) {
     const int t0 = w * V;
     T al[V], ah[V];
 #pragma unroll
     for (int e = 0; e < V; ++e) { al[e] = T(0); ah[e] = T(0); }
     if constexpr (L > 0 && SC > 0) {
-      fwd_window<T, L, FMA, SC>(buf, t0, lo, hi, al, ah);
+      fwd_window<T, L, FMA, SC, LH>(buf, t0, lo, hi, al, ah);
     } else if constexpr (L > 0) {
 #pragma unroll
-      for (int i = 0; i < L; ++i) {  // s is a multiple of V: aligned 16-byte reads
+      for (int i = 0; i < LM; ++i) {  // s is a multiple of V: aligned 16-byte reads
         const vec v = *reinterpret_cast<const vec*>(buf + t0 - i * s);
-        vmadd<FMA, kPkFwd>(al, v, lo[i]);
-        vmadd<FMA, kPkFwd>(ah, v, hi[i]);
+        if (i < L) vmadd<FMA, kPkFwd>(al, v, lo[i]);
+        if (i < LH) vmadd<FMA, kPkFwd>(ah, v, hi[i]);
         if ((i & 3) == 3) __builtin_amdgcn_sched_barrier(0);  // <= 4 reads in flight (VGPR budget)
       }
     } else {
-      fwd_vec<T, 0, FMA>(buf, t0, s, lo, hi, taps, al, ah);
+      fwd_vec<T, 0, FMA>(buf, t0, s, lo, hi, taps, al, ah, taps_hi);
     }
     emit(k, w, al, ah);
   });
@@ -637,12 +657,13 @@ __device__ __forceinline__ void fwd_row_t(const T* buf, int nvec, int s, const T
 // offset:imm.  With a run-time spacing each read pays its own address instruction (a v_lshl_add / v_add /
 // v_subrev per tap: as much issue time as a v_fma_f64).  Same taps, same order, same arithmetic as SC = 0.
 #define VW_CT_SPACINGS(X) X(2) X(4) X(8) X(16) X(32) X(64)
-template <typename T, int L, bool FMA, int NV, int S, bool FULL, typename Emit>
+template <typename T, int L, bool FMA, int NV, int S, bool FULL, int LH = L, typename Emit>
 __device__ __forceinline__ void fwd_row_ct(const T* buf, int nvec, const T* lo, const T* hi, Emit&& emit) {
   constexpr int V = VT<T>::V;
   using vec = typename VT<T>::v;
-  static_assert(S % V == 0 && (L - 1) * S * (int)sizeof(T) < 65536, "aligned reads, 16-bit offsets");
-  const T* const low = buf - (L - 1) * S;  // tap L-1, the lowest address (uniform part)
+  constexpr int LM = L > LH ? L : LH;
+  static_assert(S % V == 0 && (LM - 1) * S * (int)sizeof(T) < 65536, "aligned reads, 16-bit offsets");
+  const T* const low = buf - (LM - 1) * S;  // the last tap, the lowest address (uniform part)
   for_vecs<L, NV, FULL>(nvec, [&](int k, int w) {
     const int t0 = w * V;
     T al[V], ah[V];
@@ -650,10 +671,10 @@ __device__ __forceinline__ void fwd_row_ct(const T* buf, int nvec, const T* lo, 
     for (int e = 0; e < V; ++e) { al[e] = T(0); ah[e] = T(0); }
     const unsigned a0 = lds_base(low + t0);
 #pragma unroll
-    for (int i = 0; i < L; ++i) {
-      const vec v = lds_vec_at<vec>(a0 + (unsigned)((L - 1 - i) * S * (int)sizeof(T)));
-      vmadd<FMA, kPkFwd>(al, v, lo[i]);
-      vmadd<FMA, kPkFwd>(ah, v, hi[i]);
+    for (int i = 0; i < LM; ++i) {
+      const vec v = lds_vec_at<vec>(a0 + (unsigned)((LM - 1 - i) * S * (int)sizeof(T)));
+      if (i < L) vmadd<FMA, kPkFwd>(al, v, lo[i]);
+      if (i < LH) vmadd<FMA, kPkFwd>(ah, v, hi[i]);
       // <= 4 reads in flight, as the run-time body; 8 measured the same (profiles/r07/ab_db4_level_ct.log)
       if ((i & 3) == 3) __builtin_amdgcn_sched_barrier(0);
     }
@@ -663,22 +684,22 @@ __device__ __forceinline__ void fwd_row_ct(const T* buf, int nvec, const T* lo, 
 
 // ct: the level's spacing is dispatched ONCE per row and level to a compile-time-stride body (VW_LEVEL_CT);
 // any other spacing, and ct = 0, run the run-time-stride body.
-template <typename T, int L, bool FMA, int NV, bool FULL = false, typename Emit>
+template <typename T, int L, bool FMA, int NV, bool FULL = false, int LH = L, typename Emit>
 __device__ __forceinline__ void fwd_row(const T* buf, int nvec, int s, const T* lo, const T* hi, int taps, int ct,
-                                        Emit&& emit) {
+                                        Emit&& emit, int taps_hi = -1) {
   constexpr int V = VT<T>::V;
   if constexpr (L > 0) {
-    if (s == 1) return fwd_row_t<T, L, FMA, NV, 1, FULL>(buf, nvec, s, lo, hi, taps, emit);
+    if (s == 1) return fwd_row_t<T, L, FMA, NV, 1, FULL, LH>(buf, nvec, s, lo, hi, taps, emit);
     if constexpr (V == 4) {
-      if (s == 2) return fwd_row_t<T, L, FMA, NV, 2, FULL>(buf, nvec, s, lo, hi, taps, emit);
+      if (s == 2) return fwd_row_t<T, L, FMA, NV, 2, FULL, LH>(buf, nvec, s, lo, hi, taps, emit);
     }
   }
-  if constexpr (L > 0 && L <= 8) {
+  if constexpr (L > 0 && L <= 8 && LH <= 8) {
     if (ct) {
       switch (s) {
 #define VW_CASE(n) \
         case n:    \
-          if constexpr (n % V == 0) return fwd_row_ct<T, L, FMA, NV, n, FULL>(buf, nvec, lo, hi, emit); \
+          if constexpr (n % V == 0) return fwd_row_ct<T, L, FMA, NV, n, FULL, LH>(buf, nvec, lo, hi, emit); \
           break;
         VW_CT_SPACINGS(VW_CASE)
 #undef VW_CASE
@@ -686,7 +707,7 @@ __device__ __forceinline__ void fwd_row(const T* buf, int nvec, int s, const T* 
       }
     }
   }
-  fwd_row_t<T, L, FMA, NV, 0, FULL>(buf, nvec, s, lo, hi, taps, emit);
+  fwd_row_t<T, L, FMA, NV, 0, FULL, LH>(buf, nvec, s, lo, hi, taps, emit, taps_hi);
 }
 
 // Inverse, one branch over the row: acc[k]_e (+)= f[i] * buf[t0 + e + dir*i*s + off], i ascending
@@ -838,7 +859,7 @@ __device__ __forceinline__ void nf_flag_row(int* flag, long long b, T z) {
 }
 
 // NFP: probe the final approximation (nf: the row's accumulator, see nf_probe)
-template <typename T, int L, bool FMA, int NV, bool VALIDATE, bool NFP = false, bool FULL = false>
+template <typename T, int L, bool FMA, int NV, bool VALIDATE, bool NFP = false, bool FULL = false, int LH = L>
 __device__ __forceinline__ void fwd_level(const FwdArgs<T>& p, const T* X, int nvec, const LevelDesc& lv, T* dout,
                                           T* aout, bool vec_ok, unsigned long long flat0, T (&areg)[NV][VT<T>::V],
                                           T* nf = nullptr) {
@@ -846,7 +867,7 @@ __device__ __forceinline__ void fwd_level(const FwdArgs<T>& p, const T* X, int n
   const int N = p.N;
   // (the validating form keeps the run-time-stride body: one level body per kernel is enough there)
   const int ct = VALIDATE ? 0 : p.level_ct;
-  fwd_row<T, L, FMA, NV, FULL>(X, nvec, lv.s, p.lo, p.hi, p.taps, ct, [&](int k, int w, const T (&al)[V], const T (&ah)[V]) {
+  fwd_row<T, L, FMA, NV, FULL, LH>(X, nvec, lv.s, p.lo, p.hi, p.taps, ct, [&](int k, int w, const T (&al)[V], const T (&ah)[V]) {
     const int t0 = w * V;
     store_vec<VW_FWD_STORE_AUX, FULL>(dout, t0, N, vec_ok, ah);
     if (aout) store_vec<VW_FWD_STORE_AUX, FULL>(aout, t0, N, vec_ok, al);
@@ -859,14 +880,15 @@ __device__ __forceinline__ void fwd_level(const FwdArgs<T>& p, const T* X, int n
     }
 #pragma unroll
     for (int e = 0; e < V; ++e) areg[k][e] = al[e];
-  });
+  }, p.taps_hi);
 }
 
 // HIST: streaming history halos (kHaloHistory) possible.  The history is the only global load inside
 // the level loop; without it (HIST = false) no load can be pending there, so the waitcnt pass never
 // waits vmcnt(0) -- which on gfx950 would also wait for every detail store still in flight.
-template <typename T, int L, bool FMA, int NV, bool HIST>
-__global__ void VW_FUSED_BOUNDS(NV, VW_FUSED_W(L, 8)) k_forward_fused(const FwdArgs<T> p) {
+// LH: the high-pass tap count of a two-length bank (VW_BI; fwd_window); LH = L is the equal-length kernel.
+template <typename T, int L, bool FMA, int NV, bool HIST, int LH = L>
+__global__ void VW_FUSED_BOUNDS(NV, VW_FUSED_W((L > LH ? L : LH), 8)) k_forward_fused(const FwdArgs<T> p) {
   constexpr int V = VT<T>::V;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   T* X = reinterpret_cast<T*>(smem) + p.hlpad;
@@ -902,8 +924,8 @@ __global__ void VW_FUSED_BOUNDS(NV, VW_FUSED_W(L, 8)) k_forward_fused(const FwdA
     lds_barrier();  // X = level input + halo; every read of Y (previous level) done
     T* dout = p.details + ((size_t)(j - 1) * (size_t)p.B + (size_t)b) * (size_t)N;
     T* aout = (j == p.J) ? p.approx + b * (size_t)N : nullptr;
-    if (p.validate) fwd_level<T, L, FMA, NV, true>(p, X, nvec, lv, dout, aout, vec_ok, flat0, areg);
-    else fwd_level<T, L, FMA, NV, false>(p, X, nvec, lv, dout, aout, vec_ok, flat0, areg);
+    if (p.validate) fwd_level<T, L, FMA, NV, true, false, false, LH>(p, X, nvec, lv, dout, aout, vec_ok, flat0, areg);
+    else fwd_level<T, L, FMA, NV, false, false, false, LH>(p, X, nvec, lv, dout, aout, vec_ok, flat0, areg);
     // Streaming: new left history = last hist_len samples of this level's input
     // (BatchStreamingMODWT.updateHistoryFromSoA :337-352).
     if (HIST && p.hist_update && lv.hist_len > 0) {
@@ -1169,8 +1191,10 @@ __global__ void VW_FUSED_BOUNDS(NV, VW_FUSED_W(L, 6)) k_inverse_fused(const InvA
 //   barrier -> stage d_j (prefetched last level) into Y, prefetch d_{j-1} -> approx branch on X
 //   -> barrier -> detail branch on Y -> a_{j-1} into X
 // i.e. two workgroup barriers per level, and d_{j-1}'s loads have a whole level to land.
-template <typename T, int L, bool FMA, int NV>
-__global__ void VW_FUSED_BOUNDS(NV, VW_FUSED_W(L, 6)) k_inverse_db(const InvArgs<T> p) {
+// LH: the detail branch's compile-time tap count (two-length banks, VW_BI): each branch issues its own filter's
+// LDS reads and multiplies; LH = L is the equal-length kernel.
+template <typename T, int L, bool FMA, int NV, int LH = L>
+__global__ void VW_FUSED_BOUNDS(NV, VW_FUSED_W((L > LH ? L : LH), 6)) k_inverse_db(const InvArgs<T> p) {
   constexpr int V = VT<T>::V;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   T* const X = reinterpret_cast<T*>(smem) + p.hlpad_a;
@@ -1202,7 +1226,7 @@ __global__ void VW_FUSED_BOUNDS(NV, VW_FUSED_W(L, 6)) k_inverse_db(const InvArgs
     zero_regs<T, NV>(acc);
     inv_row<T, L, FMA, NV>(X, nvec, lv.s, lv.dir_a, lv.off_a, p.lo, p.taps, p.level_ct, acc);
     lds_barrier();  // Y = d_j + halo; every read of X done
-    inv_row<T, L, FMA, NV>(Y, nvec, lv.s, lv.dir_d, lv.off_d, p.hi, p.taps, p.level_ct, acc);
+    inv_row<T, LH, FMA, NV>(Y, nvec, lv.s, lv.dir_d, lv.off_d, p.hi, p.taps_hi, p.level_ct, acc);
     if (j > 1) regs_to_level<T, L, NV>(X, acc, nvec, N, p.lv[j - 2], 0, (const T*)nullptr);
   }
   for_vecs<L, NV>(nvec, [&](int k, int w) { store_vec<VW_INV_STORE_AUX>(p.y + b * (size_t)N, w * V, N, vec_ok, acc[k]); });
@@ -1215,8 +1239,9 @@ __global__ void VW_FUSED_BOUNDS(NV, VW_FUSED_W(L, 6)) k_inverse_db(const InvArgs
 #endif
 // FULL: aligned rows with every slab full (threads * NV == N / V; host: InvArgs::full) -- the bounds
 // checks of the row transfers and the ragged-row store path are compiled out (VW_LEVEL_CT).
-template <typename T, int L, bool FMA, int NV, bool FULL = false>
-__global__ void VW_FUSED_BOUNDS(NV, VW_FUSED_W(L, VW_INV_W)) k_inverse_seq(const InvArgs<T> p) {
+// LH: as k_inverse_db.
+template <typename T, int L, bool FMA, int NV, bool FULL = false, int LH = L>
+__global__ void VW_FUSED_BOUNDS(NV, VW_FUSED_W((L > LH ? L : LH), VW_INV_W)) k_inverse_seq(const InvArgs<T> p) {
   constexpr int V = VT<T>::V;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   T* R = reinterpret_cast<T*>(smem) + p.hlpad_a;
@@ -1251,7 +1276,7 @@ __global__ void VW_FUSED_BOUNDS(NV, VW_FUSED_W(L, VW_INV_W)) k_inverse_seq(const
       load_row_regs<T, NV, FULL>(dreg, p.details + (size_t)(j - 2) * plane + b * (size_t)N, N, nvec, vec_ok,
                            p.lv[j - 2].use_d == 0);
     lds_barrier();  // R = d_j + halo
-    inv_row<T, L, FMA, NV, FULL>(R, nvec, lv.s, lv.dir_d, lv.off_d, p.hi, p.taps, p.level_ct, acc);
+    inv_row<T, LH, FMA, NV, FULL>(R, nvec, lv.s, lv.dir_d, lv.off_d, p.hi, p.taps_hi, p.level_ct, acc);
     if (j > 1) {
       lds_barrier();  // every detail-branch read done
       regs_to_level<T, L, NV, FULL>(R, acc, nvec, N, p.lv[j - 2], 0, (const T*)nullptr);

@@ -23,8 +23,34 @@ static hipError_t run_forward_fused(const FwdArgs<T>& a, int threads, int lds, i
   return nv <= 4 ? run_forward_fused_nv<T, L, FMA, 4>(a, threads, lds, st) : run_forward_fused_nv<T, L, FMA, 8>(a, threads, lds, st);
 }
 
+// Two-length banks (FwdArgs::taps_hi != taps; the planner's VW_BI route: no history, NV = 4 / 8): the compile-time
+// pairs of VW_TAP_PAIR_LIST, else the runtime-L kernel with its two counts.
+template <typename T, int L, int LH, bool FMA, int NV>
+static hipError_t run_forward_bi_nv(const FwdArgs<T>& a, int threads, int lds, hipStream_t st) {
+  auto k = k_forward_fused<T, L, FMA, NV, false, LH>;
+  static LdsOnce configured;
+  hipError_t e = set_lds(k, lds, &configured);
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(k, dim3((unsigned)a.B), dim3(threads), lds, st, a);
+  return hipGetLastError();
+}
+template <typename T, int L, int LH>
+static hipError_t run_forward_bi(const FwdArgs<T>& a, int threads, int lds, bool fma, int nv, hipStream_t st) {
+  if (nv <= 4) return fma ? run_forward_bi_nv<T, L, LH, true, 4>(a, threads, lds, st) : run_forward_bi_nv<T, L, LH, false, 4>(a, threads, lds, st);
+  return fma ? run_forward_bi_nv<T, L, LH, true, 8>(a, threads, lds, st) : run_forward_bi_nv<T, L, LH, false, 8>(a, threads, lds, st);
+}
+
 template <typename T>
 hipError_t launch_forward_fused(const FwdArgs<T>& a, int threads, int lds, bool fma, int nv, hipStream_t st) {
+  if (a.taps_hi != a.taps) {
+    if (a.hist[0] != nullptr || nv == 2) return hipErrorInvalidValue;  // not a plan of the two-length route
+    if (a.unrolled) {
+#define VW_CASE(lo, hi) if (a.taps == lo && a.taps_hi == hi) return run_forward_bi<T, lo, hi>(a, threads, lds, fma, nv, st);
+      VW_TAP_PAIR_LIST(VW_CASE)
+#undef VW_CASE
+    }
+    return run_forward_bi<T, 0, 0>(a, threads, lds, fma, nv, st);
+  }
   switch (a.unrolled ? a.taps : 0) {  // unaligned rows / partial slabs: runtime-L kernel
 #define VW_CASE(n) \
     case n: return fma ? run_forward_fused<T, n, true>(a, threads, lds, nv, st) : run_forward_fused<T, n, false>(a, threads, lds, nv, st);

@@ -66,6 +66,8 @@ struct FwdArgs {
   T* hist[kMaxLevels];
   int hist_update;      // 1: write the new history after each level
   int taps;             // L (runtime copy; kernels are also templated on it)
+  int taps_hi;          // taps of hi: == taps, except on the two-length route (VW_BI; k_forward_fused reads each tap
+                        // position once and feeds the low sum while i < taps, the high sum while i < taps_hi)
   int tap_lds;          // k_forward_blk: element offset of the LDS tap table
   int blk_tight;        // k_forward_blk: sparse padding (blk_pad)
   int* nf_flag;         // k_forward_persist, VW_FLAG_REF_NONFINITE: nf_flag[b] = 1 when an output of row b is
@@ -98,6 +100,8 @@ struct InvArgs {
   long long thr_ld;     // level stride of thr (0: one threshold per signal for every level)
   int soft;
   int taps;
+  int taps_hi;          // taps of hi: == taps, except on the two-length route (VW_BI; k_inverse_seq / k_inverse_db run
+                        // each branch at its own count: taps = the low-pass length, taps_hi the high-pass length)
   int tap_lds;          // k_inverse_blk: element offset of the LDS tap table
   int blk_tight;        // k_inverse_blk: sparse padding (blk_pad)
   int* nf_flag;         // k_inverse_seq, VW_FLAG_REF_NONFINITE: nf_flag[b] = 1 when an input or the output of
@@ -216,7 +220,8 @@ struct RefArgs {
   long long B;
   int N;
   int J;
-  int L;
+  int L;                        // taps of lo (and of hi when Lhi == 0)
+  int Lhi;                      // biorthogonal bank: taps of hi (0 = L); each filter stops at its own upsampled length
   int mode;                     // kHaloPeriodic / kHaloZero / kHaloSymmetric
   // forward, BatchStreamingMODWT ZERO / SYMMETRIC blocks: samples left of the block come from the level's
   // history (hist_old, [B][hist_len_j] oldest first; hist_first: the history the first block initialises,

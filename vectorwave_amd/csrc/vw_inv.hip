@@ -35,8 +35,34 @@ static hipError_t run_inverse_fused(const InvArgs<T>& a, int threads, int lds, i
   return nv <= 4 ? run_inverse_fused_nv<T, L, FMA, 4>(a, threads, lds, st) : run_inverse_fused_nv<T, L, FMA, 8>(a, threads, lds, st);
 }
 
+// Two-length banks (InvArgs::taps_hi != taps; the planner's VW_BI route: sequential sums, NV = 4 / 8): each branch
+// at its own tap count -- the compile-time pairs of VW_TAP_PAIR_LIST, else the runtime-L kernel with its two counts.
+template <typename T, int L, int LH, bool FMA, int NV>
+static hipError_t run_inverse_bi_nv(const InvArgs<T>& a, int threads, int lds, hipStream_t st) {
+  static LdsOnce configured_seq, configured_db;
+  auto k = a.db ? k_inverse_db<T, L, FMA, NV, LH> : k_inverse_seq<T, L, FMA, NV, false, LH>;
+  hipError_t e = set_lds(k, lds, a.db ? &configured_db : &configured_seq);
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(k, dim3((unsigned)a.B), dim3(threads), lds, st, a);
+  return hipGetLastError();
+}
+template <typename T, int L, int LH>
+static hipError_t run_inverse_bi(const InvArgs<T>& a, int threads, int lds, bool fma, int nv, hipStream_t st) {
+  if (nv <= 4) return fma ? run_inverse_bi_nv<T, L, LH, true, 4>(a, threads, lds, st) : run_inverse_bi_nv<T, L, LH, false, 4>(a, threads, lds, st);
+  return fma ? run_inverse_bi_nv<T, L, LH, true, 8>(a, threads, lds, st) : run_inverse_bi_nv<T, L, LH, false, 8>(a, threads, lds, st);
+}
+
 template <typename T>
 hipError_t launch_inverse_fused(const InvArgs<T>& a, int threads, int lds, bool fma, int nv, hipStream_t st) {
+  if (a.taps_hi != a.taps) {
+    if (a.pair || a.blk || nv == 2) return hipErrorInvalidValue;  // not a plan of the two-length route
+    if (a.unrolled) {
+#define VW_CASE(lo, hi) if (a.taps == lo && a.taps_hi == hi) return run_inverse_bi<T, lo, hi>(a, threads, lds, fma, nv, st);
+      VW_TAP_PAIR_LIST(VW_CASE)
+#undef VW_CASE
+    }
+    return run_inverse_bi<T, 0, 0>(a, threads, lds, fma, nv, st);
+  }
   switch (a.unrolled ? a.taps : 0) {  // unaligned rows / partial slabs: runtime-L kernel
 #define VW_CASE(n) \
     case n: return fma ? run_inverse_fused<T, n, true>(a, threads, lds, nv, st) : run_inverse_fused<T, n, false>(a, threads, lds, nv, st);

@@ -59,6 +59,8 @@ static const TuningKey kTuningTable[] = {
     VW_KEY("VW_REF_GRID", t.ref_grid = v < 0 ? d.ref_grid : v),
     VW_KEY("VW_LEVEL_CT", t.level_ct = v < 0 ? d.level_ct : v != 0),
     VW_KEY("VW_ENERGY_FUSED", t.energy_fused = v < 0 ? d.energy_fused : v),
+    VW_KEY("VW_BI", t.bi = v < 0 ? d.bi : v & 7),
+    VW_KEY("VW_BI_LISTED", t.bi_listed = v < 0 ? d.bi_listed : v != 0),
 };
 #undef VW_KEY
 
@@ -450,10 +452,15 @@ static void reserve_ref(const Tuning& tu, int cus, int64_t B, int64_t N, P* p) {
 // ------------------------------------------------------------------------------------------------
 // Forward (multi-level and single-level share this path).
 
-// Level descriptors of the forward; returns the longest left halo.
+// Level descriptors of the forward; returns the longest left halo.  c.L is the kernels' tap count (the longer
+// filter of a two-length bank); Llo / Lhi the filters' own lengths (0 = c.L), which decide the FFT-switch mode:
+// the outer gate reads the low-pass length, behind it each filter takes the FFT branch by its own length.
+// *mixed = the first level where exactly one of them does (0 = none).
 template <typename T>
-static int forward_levels(const FwdCall<T>& c, LevelDesc* lv) {
+static int forward_levels(const FwdCall<T>& c, LevelDesc* lv, int Llo = 0, int Lhi = 0, int* mixed = nullptr) {
   int max_hl = 0;
+  if (Llo <= 0) Llo = c.L;
+  if (Lhi <= 0) Lhi = c.L;
   for (int j = 1; j <= c.J; ++j) {
     LevelDesc& d = lv[j - 1];
     memset(&d, 0, sizeof(d));
@@ -464,10 +471,14 @@ static int forward_levels(const FwdCall<T>& c, LevelDesc* lv) {
     d.hist_len = (int)(Lj - 1);
     if (c.boundary == VW_PERIODIC) {
       d.mode = kHaloPeriodic;
-      // MultiLevelMODWTTransform.applyScaledMODWT :734-742 + FftHeuristics :30-34
-      if ((c.flags & VW_FLAG_FFT_SWITCH) && !c.single_level && !(c.N < 64 || Lj > c.N / 2) && c.N >= 1024 &&
-          (double)Lj > c.N * (1.0 / 8.0) && !is_pow2(c.N))
-        d.mode = kHaloFftPad;
+      // MultiLevelMODWTTransform.applyScaledMODWT :734-742 + WaveletOperations :31-33 + FftHeuristics :30-34
+      const int64_t Llo_j = upsampled_length(Llo, j), Lhi_j = upsampled_length(Lhi, j);
+      if ((c.flags & VW_FLAG_FFT_SWITCH) && !c.single_level && !(c.N < 64 || Llo_j > c.N / 2) && c.N >= 1024 &&
+          !is_pow2(c.N)) {
+        const bool fft_lo = (double)Llo_j > c.N * (1.0 / 8.0), fft_hi = (double)Lhi_j > c.N * (1.0 / 8.0);
+        if (fft_lo && fft_hi) d.mode = kHaloFftPad;
+        else if (fft_lo != fft_hi && mixed && !*mixed) *mixed = j;
+      }
     } else {
       d.mode = c.boundary == VW_ZERO_PADDING ? kHaloZero : kHaloSymmetric;
     }
@@ -489,7 +500,7 @@ static int forward_levels(const FwdCall<T>& c, LevelDesc* lv) {
 // Its contract: two buffers, full slabs of whole waves, rows in 64-vector chunks, no validation
 // or streaming history.  VW_FWD_PERSIST=0 disables it.
 template <typename T>
-static bool plan_forward_fused(const Tuning& tu, const FwdCall<T>& c, int max_hl, FwdPlan<T>* p) {
+static bool plan_forward_fused(const Tuning& tu, const FwdCall<T>& c, int max_hl, FwdPlan<T>* p, bool bi = false) {
   constexpr int V = vec_width<T>();
   const int64_t N = c.N, nvec = (N + V - 1) / V;
   const int L = c.L, J = c.J;
@@ -500,14 +511,14 @@ static bool plan_forward_fused(const Tuning& tu, const FwdCall<T>& c, int max_hl
       (c.ldx % V == 0) && (N % V == 0) && aligned16(c.x) && aligned16(c.details) && aligned16(c.approx);
   int threads = 0, lds = 0, nv = 4;
   auto persist_ok = [&](int th, int nvv, bool ft) {
-    return tu.fwd_persist && io_aligned && ft && nvv == 4 && !validate && !hist && (int64_t)th * nvv == nvec &&
+    return !bi && tu.fwd_persist && io_aligned && ft && nvv == 4 && !validate && !hist && (int64_t)th * nvv == nvec &&
            th % 64 == 0 && nvec % 64 == 0 && has_unrolled_taps(L) && J >= 1;
   };
   const int64_t region = round_up(hlpad + nvec * V + V, V);
   bool dbl = tu.fwd_buf ? tu.fwd_buf == 2 : true;
   bool fused = false, fit = false;
   // NV = 2 (1024-thread workgroups) only where the unrolled kernel will run (it has no runtime-L form)
-  const int fwd_nv2 = (tu.fwd_nv == 2 && io_aligned && L <= 8 && L <= tu.unroll_max && has_unrolled_taps(L) &&
+  const int fwd_nv2 = (!bi && tu.fwd_nv == 2 && io_aligned && L <= 8 && L <= tu.unroll_max && has_unrolled_taps(L) &&
                        !(tu.blk > 0 && L >= tu.blk)) ? 2 : 0;
   if (J <= kMaxLevels && !tu.force_tiled) {
     if (dbl) dbl = fused_plan(tu, N, V, sizeof(T), 2 * region, &threads, &nv, &lds, &fit, fwd_nv2);
@@ -535,7 +546,7 @@ static bool plan_forward_fused(const Tuning& tu, const FwdCall<T>& c, int max_hl
   // spills) the blocked forward beats the fused one at sym8 N = 16384: 5.27-5.29 -> 4.76 ms,
   // profiles/r04/ab_blk_fwd8_ktaps_sym8.log; VW_BLK_FWD8=0 restores the fused kernel)
   // (listed tap counts only: launch_forward_blk has no runtime-L form)
-  if (tu.blk > 0 && L >= tu.blk && has_unrolled_taps(L) && a.unrolled && !validate && !hist &&
+  if (!bi && tu.blk > 0 && L >= tu.blk && has_unrolled_taps(L) && a.unrolled && !validate && !hist &&
       (int64_t)threads * nv == nvec && (nv == 4 || (nv == 8 && tu.blk_fwd8))) {
     const BlkPlan b = blk_plan<T>(a.lv, J, L, nvec, nv, false);
     a.blk_tight = b.tight;
@@ -553,7 +564,7 @@ static bool plan_forward_fused(const Tuning& tu, const FwdCall<T>& c, int max_hl
   }
   // fp32 FMA, PERIODIC, long filters: the matrix-core forward (vw_mfma.hip, VW_MFMA bit 0)
   if (std::is_same<T, float>::value) {
-    bool ok = (tu.mfma & 1) && p->fma && !c.single_level && a.vec_io && !validate && !hist;
+    bool ok = !bi && (tu.mfma & 1) && p->fma && !c.single_level && a.vec_io && !validate && !hist;
     for (int j = 0; ok && j < J; ++j) ok = a.lv[j].mode == kHaloPeriodic;
     const int scratch = 8 * 256 + 4;  // the forward's per-wave transpose scratch (<= 8 waves), aligned
     if (const int mfma_lds = mfma_layout(ok, L, J, N, scratch, &a.hlpad, &a.tap_lds)) {
@@ -649,8 +660,25 @@ static void plan_forward_levels(const Tuning& tu, const FwdCall<T>& c, FwdPlan<T
   p->nf_probed = !p->steps.empty() && p->steps.back().probe;
 }
 
+template <typename C>
+static int hi_taps(const C& c) { return c.Lhi > 0 ? c.Lhi : c.L; }
+
+// Tap count the kernels run for a bank whose longer filter has `L` taps.  Most biorthogonal lengths are odd and
+// none of those is in VW_TAP_LIST, so max(Llo, Lhi) would run the runtime-L kernels; one more zero tap reaches a
+// listed count and with it the tap-unrolled, persistent, register-blocked, deep and sweep kernels (VW_BI_LISTED).
+// The extra tap changes no bit (as every padded tap) and only lengthens the halos, which every path below sizes
+// from the tap count it is given; a plan that fails with it is planned again without (plan_forward / plan_inverse).
+static int listed_taps(const Tuning& tu, int L, bool two_lengths) {
+  return (two_lengths && tu.bi_listed && !has_unrolled_taps(L) && L < kMaxTaps && has_unrolled_taps(L + 1)) ? L + 1 : L;
+}
+
 template <typename T>
-void plan_forward(const Tuning& tu, const FwdCall<T>& c, FwdPlan<T>* p) {
+static void plan_forward_taps(const Tuning& tu, const FwdCall<T>& call, int taps, FwdPlan<T>* p, bool bi = false) {
+  // two lengths: the padded route (vw_plan.h) -- every kernel below sees one tap count
+  FwdCall<T> c = call;
+  const int Llo = call.L, Lhi = hi_taps(call);
+  c.L = taps;
+  c.Lhi = 0;
   const bool hist = c.hist != nullptr;
   p->fma = c.flags & VW_FLAG_FMA;
   p->validate = c.flags & VW_FLAG_VALIDATE;
@@ -659,16 +687,30 @@ void plan_forward(const Tuning& tu, const FwdCall<T>& c, FwdPlan<T>* p) {
   a.npow2 = next_pow2(c.N);
   a.validate = p->validate;
   a.hist_update = c.hist_update ? 1 : 0;
-  a.taps = c.L;
-  const int max_hl = forward_levels(c, a.lv);
+  a.taps = c.L; a.taps_hi = c.L;
+  int mixed = 0;
+  const int max_hl = forward_levels(c, a.lv, Llo, Lhi, &mixed);
+  if (mixed)
+    return plan_error(p, VW_ERR_UNSUPPORTED, "FFT switch: one filter of level %d is in the FFT region, one is not (mixed level)",
+                      mixed);
   // VW_FLAG_REF_NONFINITE on a streaming block: keep the histories this block reads (the kernels
   // overwrite them) for the rows vw_ref.hip recomputes
   p->snapshot = (c.flags & VW_FLAG_REF_NONFINITE) && hist && c.hist_update && c.hist_snap && !c.hist_first && c.J >= 2;
   // the unvalidated callers' NaN spread through the zero taps (single level and J = 1 have none); a
   // streaming block that updates its history needs the snapshot of the histories it read (stream_run)
-  p->ref_nf = (c.flags & VW_FLAG_REF_NONFINITE) && !p->validate && !c.single_level && c.J >= 2 &&
+  // A zero-extended filter has zero taps at level 1 too, where the reference's loops read nothing: there the
+  // fix-up also covers J = 1 and the single-level forward.
+  const bool padded = taps != Llo || taps != Lhi;
+  p->ref_nf = (c.flags & VW_FLAG_REF_NONFINITE) && !p->validate && (padded || (!c.single_level && c.J >= 2)) &&
               !(c.flags & VW_FLAG_FFT_SWITCH) && (!hist || !c.hist_update || c.hist_first || c.hist_snap);
-  p->fused = plan_forward_fused(tu, c, max_hl, p);
+  p->fused = plan_forward_fused(tu, c, max_hl, p, bi);
+  // the two-length route: planned for the longer reach, run at each filter's own count (unrolled only for a listed pair)
+  // -- and by default only there: the runtime-L bodies lose to the padded route's unrolled kernels (VW_BI bit 2)
+  if (bi && p->fused && !hist && p->nv != 2 && p->kernel == kFwdFused &&
+      ((tu.bi & 4) || (a.unrolled && has_unrolled_pair(Llo, Lhi)))) {
+    a.taps = Llo; a.taps_hi = Lhi;
+    a.unrolled = a.unrolled && has_unrolled_pair(Llo, Lhi);
+  }
   if (!p->fused) plan_forward_levels(tu, c, p);
   reserve_ref<T>(tu, c.cus, c.B, c.N, p);
 }
@@ -729,8 +771,10 @@ void plan_energy(const Tuning& tu, const FwdCall<double>& c, EnergyPlan* p) {
 // Inverse
 
 // Level descriptors of the inverse; the longest halos come back through max_hl / max_hr.
+// c.L is the kernels' tap count, which bounds the reach of both branches; Llo / Lhi are the reconstruction
+// filters' own lengths: decide() keys on the low-pass one, each branch shifts by its own tau (:604-608).
 template <typename T>
-static void inverse_levels(const InvCall<T>& c, LevelDesc* lv, int* max_hl, int* max_hr) {
+static void inverse_levels(const InvCall<T>& c, int Llo, int Lhi, LevelDesc* lv, int* max_hl, int* max_hr) {
   constexpr int V = vec_width<T>();
   const int tmax = (int)((c.N + V - 1) / V * V - 1);
   for (int j = 1; j <= c.J; ++j) {
@@ -741,9 +785,9 @@ static void inverse_levels(const InvCall<T>& c, LevelDesc* lv, int* max_hl, int*
     d.mode = ref_mode(c.boundary);
     if (c.boundary == VW_SYMMETRIC && !c.single_level) {
       int ap, dh, dp, dg;
-      sym_decide(c.wid, c.L, j, &ap, &dh, &dp, &dg);
-      const int tauH = compute_tau(c.L, j) + dh;
-      const int tauG = compute_tau(c.L, j) + dg;
+      sym_decide(c.wid, Llo, j, &ap, &dh, &dp, &dg);
+      const int tauH = compute_tau(Llo, j) + dh;
+      const int tauG = compute_tau(Lhi, j) + dg;
       d.dir_a = ap ? 1 : -1; d.off_a = ap ? -tauH : tauH;
       d.dir_d = dp ? 1 : -1; d.off_d = dp ? -tauG : tauG;
     } else if (c.boundary == VW_SYMMETRIC) {
@@ -780,7 +824,7 @@ static void inverse_levels(const InvCall<T>& c, LevelDesc* lv, int* max_hl, int*
 // dispatch of one-signal workgroups balances better.)
 template <typename T>
 static bool plan_inverse_fused(const Tuning& tu, const InvCall<T>& c, bool pair, int max_hl, int max_hr,
-                               InvPlan<T>* p) {
+                               InvPlan<T>* p, bool bi = false) {
   constexpr int V = vec_width<T>();
   const int64_t N = c.N, nvec = (N + V - 1) / V;
   const int L = c.L, J = c.J;
@@ -789,7 +833,8 @@ static bool plan_inverse_fused(const Tuning& tu, const InvCall<T>& c, bool pair,
   const int hlpad = (int)round_up(max_hl, V);
   const int64_t region = round_up(hlpad + nvec * V + max_hr + V, V);
   int threads = 0, lds = 0, nv = 4;
-  const bool blk_pref = tu.blk > 0 && L >= tu.blk && has_unrolled_taps(L) && periodic;
+  // bi: the two-length route keeps to k_inverse_seq / k_inverse_db (no register-blocked or matrix-core form)
+  const bool blk_pref = !bi && tu.blk > 0 && L >= tu.blk && has_unrolled_taps(L) && periodic;
   bool db = !pair && (tu.inv_buf ? tu.inv_buf == 2 : (c.B <= 2LL * c.cus && !blk_pref));
   bool fused = false, fit = false;
   const bool inv_io = (N % V == 0) && aligned16(c.details) && aligned16(c.approx) && aligned16(c.y);
@@ -813,7 +858,7 @@ static bool plan_inverse_fused(const Tuning& tu, const InvCall<T>& c, bool pair,
   a.full = tu.level_ct && a.unrolled && (int64_t)threads * nv == nvec;
   p->kernel = pair ? kInvPair : db ? kInvDb : kInvSeq;
   // register-blocked PERIODIC inverse for long filters (vw_blk.h k_inverse_blk)
-  if (tu.blk > 0 && L >= tu.blk && has_unrolled_taps(L) && nv != 2 && !pair && !db && periodic && a.unrolled &&
+  if (!bi && tu.blk > 0 && L >= tu.blk && has_unrolled_taps(L) && nv != 2 && !pair && !db && periodic && a.unrolled &&
       (int64_t)threads * nv == nvec) {
     const BlkPlan b = blk_plan<T>(a.lv, J, L, nvec, nv, true);
     a.blk_tight = b.tight;
@@ -826,7 +871,7 @@ static bool plan_inverse_fused(const Tuning& tu, const InvCall<T>& c, bool pair,
   }
   // fp32 FMA, PERIODIC sequential sums, long filters: the matrix-core inverse (vw_mfma.hip, VW_MFMA bit 1)
   if (std::is_same<T, float>::value) {
-    bool ok = (tu.mfma & 2) && p->fma && !pair && periodic && a.vec_io;
+    bool ok = !bi && (tu.mfma & 2) && p->fma && !pair && periodic && a.vec_io;
     for (int j = 0; ok && j < J; ++j) ok = plus_zero(a.lv[j]);
     if (const int mfma_lds = mfma_layout(ok, L, J, N, 0, &a.hlpad_a, &a.tap_lds)) {
       lds = mfma_lds;
@@ -989,20 +1034,72 @@ static void plan_inverse_levels(const Tuning& tu, const InvCall<T>& c, bool pair
   p->nf_probed = !p->steps.empty() && p->steps.back().probe;
 }
 
+// `taps`: the sequential sums' tap count (>= both lengths); the pairwise sums run the low-pass length
 template <typename T>
-void plan_inverse(const Tuning& tu, const InvCall<T>& c, InvPlan<T>* p) {
-  p->fma = c.flags & VW_FLAG_FMA;
+static void plan_inverse_taps(const Tuning& tu, const InvCall<T>& call, int taps, InvPlan<T>* p, bool bi = false) {
+  InvCall<T> c = call;
+  const int Llo = call.L, Lhi = hi_taps(call);
   const bool pair = c.single_level || c.boundary == VW_ZERO_PADDING;
+  // two lengths (vw_plan.h): the pairwise sums run over l < Llo and read high[l] (:591-601, MODWTTransform.inverse
+  // :203-299) -- the longer high-pass truncated, a shorter one an ArrayIndexOutOfBoundsException in the reference;
+  // the sequential sums take the padded route
+  if (pair && Lhi < Llo)
+    return plan_error(p, VW_ERR_UNSUPPORTED, "pairwise inverse: the reference indexes past its high-pass array (%d < %d taps)",
+                      Lhi, Llo);
+  c.L = pair ? Llo : taps;
+  c.Lhi = 0;
+  p->fma = c.flags & VW_FLAG_FMA;
   // the unvalidated callers' NaN spread through the zero taps (single level and J = 1 have none)
-  p->ref_nf = (c.flags & VW_FLAG_REF_NONFINITE) && !c.single_level && c.J >= 2;
+  // -- nor do the pairwise sums, whose longer high-pass is truncated; a zero-extended filter of the sequential
+  // sums has zero taps at level 1 too, so there the fix-up also covers J = 1
+  const bool padded = !pair && (c.L != Llo || c.L != Lhi);
+  p->ref_nf = (c.flags & VW_FLAG_REF_NONFINITE) && (padded || (!c.single_level && c.J >= 2));
   InvArgs<T>& a = p->args;
   a.B = c.B; a.N = (int)c.N; a.J = c.J;
-  a.approx_zero = c.approx_zero; a.thr_ld = c.thr_ld; a.soft = c.soft; a.taps = c.L;
+  a.approx_zero = c.approx_zero; a.thr_ld = c.thr_ld; a.soft = c.soft; a.taps = c.L; a.taps_hi = c.L;
   int max_hl = 0, max_hr = 0;
-  inverse_levels(c, a.lv, &max_hl, &max_hr);
-  p->fused = plan_inverse_fused(tu, c, pair, max_hl, max_hr, p);
+  inverse_levels(c, Llo, Lhi, a.lv, &max_hl, &max_hr);
+  p->fused = plan_inverse_fused(tu, c, pair, max_hl, max_hr, p, bi);
+  // the two-length route: planned for the longer reach, run at each branch's own count (unrolled only for a listed pair)
+  // -- and by default only there: the runtime-L bodies lose to the padded route's unrolled kernels (VW_BI bit 2)
+  if (bi && p->fused && !pair && p->nv != 2 && (p->kernel == kInvSeq || p->kernel == kInvDb) &&
+      ((tu.bi & 4) || (a.unrolled && has_unrolled_pair(Llo, Lhi)))) {
+    a.taps = Llo; a.taps_hi = Lhi;
+    a.unrolled = a.unrolled && has_unrolled_pair(Llo, Lhi);
+    a.full = 0;
+  }
   if (!p->fused) plan_inverse_levels(tu, c, pair, p);
   reserve_ref<T>(tu, c.cus, c.B, c.N, p);
+}
+
+template <typename T>
+void plan_forward(const Tuning& tu, const FwdCall<T>& c, FwdPlan<T>* p) {
+  const int Lmax = std::max(c.L, hi_taps(c)), taps = listed_taps(tu, Lmax, c.L != hi_taps(c));
+  if ((tu.bi & 1) && c.L != hi_taps(c) && !c.hist) {  // the two-length route where it applies (vw_plan.h)
+    plan_forward_taps(tu, c, Lmax, p, true);
+    if (p->error != VW_OK || p->args.taps_hi != p->args.taps) return;  // (a mixed FFT-switch level: refused on either route)
+    *p = FwdPlan<T>();
+  }
+  plan_forward_taps(tu, c, taps, p);
+  if (p->error != VW_OK && taps != Lmax) {
+    *p = FwdPlan<T>();
+    plan_forward_taps(tu, c, Lmax, p);
+  }
+}
+
+template <typename T>
+void plan_inverse(const Tuning& tu, const InvCall<T>& c, InvPlan<T>* p) {
+  const int Lmax = std::max(c.L, hi_taps(c)), taps = listed_taps(tu, Lmax, c.L != hi_taps(c));
+  if ((tu.bi & 2) && c.L != hi_taps(c)) {  // the two-length route where it applies (vw_plan.h), else the padded route below
+    plan_inverse_taps(tu, c, Lmax, p, true);
+    if (p->error == VW_OK && p->args.taps_hi != p->args.taps) return;
+    *p = InvPlan<T>();
+  }
+  plan_inverse_taps(tu, c, taps, p);
+  if (p->error != VW_OK && taps != Lmax) {
+    *p = InvPlan<T>();
+    plan_inverse_taps(tu, c, Lmax, p);
+  }
 }
 
 template void plan_forward<float>(const Tuning&, const FwdCall<float>&, FwdPlan<float>*);

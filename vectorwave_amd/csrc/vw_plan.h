@@ -63,6 +63,13 @@ struct Tuning {
                                // cores (vw_mfma.hip)
   int energy_fused = 1;        // VW_ENERGY_FUSED=0: vw_modwt_energy_f64 never runs the fused energy kernel (forward
                                // into the workspace, then the plane sums), also under VW_FLAG_TREE_SUMS
+  int bi = 3;                  // VW_BI=0: two-length banks on the padded route only; bit 0: the fused forward
+                               // (k_forward_fused), bit 1: the sequential fused inverses (k_inverse_seq / k_inverse_db)
+                               // run each filter at its own tap count where they fit (1 | 2 | 3, as VW_MFMA) and
+                               // the pair has compile-time kernels (VW_TAP_PAIR_LIST); bit 2: every other pair too, on
+                               // the runtime-L bodies (measured 2-3 x slower than the padded route's unrolled kernels)
+  int bi_listed = 1;           // VW_BI_LISTED=0: a two-length bank runs max(Llo, Lhi) taps even where that count is not in
+                               // VW_TAP_LIST (the runtime-L kernels); 1: one more zero tap where that reaches a listed count
 };
 
 // One switch of the Tuning struct by its environment name; value < 0 = the default.  Returns false
@@ -96,6 +103,7 @@ struct FwdCall {
   T* const* hist_snap = nullptr; // VW_FLAG_REF_NONFINITE: where the histories this block reads are kept
   bool hist_first = false;
   int cus = 256;                 // compute units of the device
+  int Lhi = 0;                   // biorthogonal bank: taps of `hi` when they differ from L, those of `lo` (0 = L)
 };
 
 template <typename T>
@@ -115,6 +123,7 @@ struct InvCall {
   int soft = 0;
   int64_t thr_ld = 0;
   int cus = 256;
+  int Lhi = 0;                   // biorthogonal bank: taps of `hi` when they differ from L, those of `lo` (0 = L)
 };
 
 // ------------------------------------------------------------------------------------------------
@@ -181,6 +190,21 @@ struct EnergyPlan {
 };
 void plan_energy(const Tuning& tu, const FwdCall<double>& c, EnergyPlan* p);
 
+// Banks with two lengths (Lhi != 0 and != L; the _bi_ entry points) run the same kernels on the PADDED ROUTE: the
+// shorter filter is zero-extended to args.taps = max(L, Lhi), or one tap further where only that count has
+// tap-unrolled kernels (VW_BI_LISTED, vw_plan.cpp listed_taps) -- for finite data a trailing 0 * x adds +-0 to a
+// sum that started at +0.0, the same bits -- while the bookkeeping keeps the true lengths: the FFT-switch mode
+// per filter (a level where exactly one filter takes the reference's FFT branch is VW_ERR_UNSUPPORTED), the
+// SYMMETRIC shifts tau(L) / tau(Lhi) per branch, halos over the longer reach.  The pairwise inverses (single
+// level, ZERO_PADDING) loop over l < L and read hi[l]: args.taps = L with hi truncated when Lhi >= L,
+// VW_ERR_UNSUPPORTED when Lhi < L (the reference indexes past its high-pass array).  The executor copies the
+// taps accordingly (vw_capi.cpp copy_bank).
+// TWO-LENGTH ROUTE (VW_BI): where the non-persistent fused forward (k_forward_fused, no history) or the fused
+// sequential-sum inverse (k_inverse_seq / k_inverse_db) fits at NV = 4 / 8, args.taps = L and args.taps_hi = Lhi.  The
+// forward reads each tap position once and feeds the low sum while i < L, the high sum while i < Lhi; each inverse
+// branch issues its own filter's LDS reads (bior3.9's synthesis 4 + 20 against the padded route's 20 + 20).  Halos are
+// still sized for the longer reach.  The persistent, register-blocked and matrix-core kernels, the per-level path and
+// the pairwise sums stay on the padded route.
 // `p` must be a freshly constructed plan.
 template <typename T> void plan_forward(const Tuning& tu, const FwdCall<T>& c, FwdPlan<T>* p);
 template <typename T> void plan_inverse(const Tuning& tu, const InvCall<T>& c, InvPlan<T>* p);

@@ -104,10 +104,13 @@ __global__ void __launch_bounds__(512) k_ref_forward(RefArgs<T> a) {
         if (ho) return ho[p];
         return a.mode == kHaloZero ? T(0) : cur[ref_sym(p - hl, N)];  // fillSymmetricHistoryFromSoA :326-335
       };
+      // two lengths: each filter is convolved over its own upsampled length (applyScaledMODWT :731-754)
+      const int Lhi = a.Lhi > 0 ? a.Lhi : a.L, Lmax = max(a.L, Lhi);
+      const int lo_len = (a.L - 1) * s + 1, hi_len = (Lhi - 1) * s + 1;
       for (int t = threadIdx.x; t < N; t += blockDim.x) {
         T sa = T(0), sd = T(0);
-        for (int i = 0; i < a.L; ++i) {
-          const int reps = (i < a.L - 1) ? s : 1;  // the zeros between tap i and tap i + 1
+        for (int i = 0; i < Lmax; ++i) {
+          const int reps = (i < Lmax - 1) ? s : 1;  // the zeros between tap i and tap i + 1
           for (int r = 0; r < reps; ++r) {
             const int l = i * s + r;
             int idx = t - l;
@@ -122,8 +125,8 @@ __global__ void __launch_bounds__(512) k_ref_forward(RefArgs<T> a) {
               v = cur[idx];
             }
             const T fl = r == 0 ? a.lo[i] : T(0), fh = r == 0 ? a.hi[i] : T(0);
-            sa = sa + fl * v;
-            sd = sd + fh * v;
+            if (l < lo_len) sa = sa + fl * v;
+            if (l < hi_len) sd = sd + fh * v;
           }
         }
         out_a[t] = sa;
@@ -147,7 +150,8 @@ __global__ void __launch_bounds__(512) k_ref_forward(RefArgs<T> a) {
 // :554-645; VectorWaveSwtAdapter.reconstructPeriodic :444-474).  Per level j with a = running
 // approximation, d = thresholded d_j (or the zero row of a masked level):
 //   PERIODIC  sum += h[l] * a[(t + l) % n] for every l, then sum += g[l] * d[(t + l) % n]  (K4)
-//   ZERO      for l with t + l < n: sum += h[l] * a[t + l] + g[l] * d[t + l]            (K5, pairwise)
+//   ZERO      for l with t + l < n: sum += h[l] * a[t + l] + g[l] * d[t + l]            (K5, pairwise: l runs
+//             over the low-pass length alone; a longer high-pass arrives truncated to it, vw_plan.h)
 //   SYMMETRIC approx branch idx = t + dir_a*l + off_a, detail branch t + dir_d*l + off_d, mirrored (K6)
 template <typename T>
 __global__ void __launch_bounds__(512) k_ref_inverse(RefArgs<T> a) {
@@ -185,8 +189,9 @@ __global__ void __launch_bounds__(512) k_ref_inverse(RefArgs<T> a) {
           for (int br = 0; br < 2; ++br) {
             const T* f = br == 0 ? a.lo : a.hi;
             const int dir = br == 0 ? lv.dir_a : lv.dir_d, off = br == 0 ? lv.off_a : lv.off_d;
-            for (int i = 0; i < a.L; ++i) {
-              const int reps = (i < a.L - 1) ? s : 1;
+            const int Lb = (br == 1 && a.Lhi > 0) ? a.Lhi : a.L;  // each branch over its own filter (:580-587, :612-639)
+            for (int i = 0; i < Lb; ++i) {
+              const int reps = (i < Lb - 1) ? s : 1;
               for (int r = 0; r < reps; ++r) {
                 const int l = i * s + r;
                 int idx;

@@ -22,6 +22,19 @@ inline bool has_unrolled_taps(int L) {
   }
 }
 
+// Banks with two filter lengths (biorthogonal): (low-pass, high-pass) tap counts with compile-time instantiations
+// of the two-length fused forward (vw_fwd.hip launch_forward_fused) and sequential inverses (vw_inv.hip
+// launch_inverse_fused) -- bior4.4 / rbio4.4 and bior2.2 / rbio2.2, analysis and synthesis pairs alike; read by
+// both launchers and by the planner (has_unrolled_pair).  Every other pair runs the runtime-L bodies with its two
+// counts (VW_BI bit 2), or the padded route.
+#define VW_TAP_PAIR_LIST(X) X(7, 9) X(9, 7) X(3, 5) X(5, 3)
+inline bool has_unrolled_pair(int Llo, int Lhi) {
+#define VW_CASE(a, b) if (Llo == a && Lhi == b) return true;
+  VW_TAP_PAIR_LIST(VW_CASE)
+#undef VW_CASE
+  return false;
+}
+
 // Matrix-core fp32 kernels (vw_mfma.hip): which (L, N) are instantiated, the halo a level set needs, and
 // the LDS floats of the kernels' padded level region for elements [0, n) (the tap table follows it).
 #ifndef VW_MFMA_PAD_SHIFT

@@ -13,7 +13,7 @@ import enum
 from . import _native as nat
 from .errors import ErrorCode, InvalidArgumentException
 from .modwt import BoundaryMode, _check_boundary, _engine_for, _validate_signal
-from .wavelets import Daubechies, Wavelet
+from .wavelets import Daubechies, Wavelet, require_orthogonal
 
 
 class ThresholdMethod(enum.IntEnum):
@@ -52,6 +52,7 @@ class WaveletDenoiser:
         if boundaryMode is None:
             raise InvalidArgumentException("boundaryMode cannot be null", ErrorCode.VAL_NULL_ARGUMENT)
         _check_boundary(BoundaryMode(boundaryMode))
+        require_orthogonal(wavelet, "WaveletDenoiser")
         self.wavelet = wavelet
         self.boundaryMode = BoundaryMode(boundaryMode)
         self._fma = nat.FLAG_FMA if fma else 0

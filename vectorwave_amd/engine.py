@@ -16,7 +16,7 @@ from typing import Optional, Sequence, Tuple
 import numpy as np
 
 from . import _native as nat
-from .errors import raise_for_status
+from .errors import InvalidArgumentException, raise_for_status
 
 try:  # torch is plumbing only (device memory, streams); optional for host-memory use
     import torch
@@ -26,6 +26,15 @@ except Exception:  # pragma: no cover
 
 def _is_device_tensor(a) -> bool:
     return torch is not None and isinstance(a, torch.Tensor) and a.is_cuda
+
+
+def _one_length(lo, hi, what: str) -> int:
+    """The tap count of a call whose ABI takes ONE length for both filters: the C side reads that many doubles of each
+    array, so a bank of two lengths must not reach it."""
+    if len(lo) != len(hi):
+        raise InvalidArgumentException(f"{what} takes one filter length, got {len(lo)} low-pass and {len(hi)} "
+                                       f"high-pass taps")
+    return len(lo)
 
 
 def _check(status: int) -> None:
@@ -179,6 +188,11 @@ class Engine:
         B, N = (1, xa.shape[0]) if one else xa.shape
         det = self._empty(xa, dev, (levels, N) if one else (levels, B, N))
         app = self._empty(xa, dev, (N,) if one else (B, N))
+        if len(lo) != len(hi):  # a biorthogonal bank: the analysis pair (vw_modwt_forward_bi_*)
+            fn = self.lib.vw_modwt_forward_bi_f32 if f32 else self.lib.vw_modwt_forward_bi_f64
+            _check(fn(self.ctx, xp, B, N, N, nat.taps_array(lo), len(lo), nat.taps_array(hi), len(hi), wavelet_id,
+                      boundary, levels, self._flags(flags, dev), self._ptr(det, dev), self._ptr(app, dev)))
+            return det, app
         fn = self.lib.vw_modwt_forward_f32 if f32 else self.lib.vw_modwt_forward_f64
         _check(fn(self.ctx, xp, B, N, N, nat.taps_array(lo), nat.taps_array(hi), len(lo), wavelet_id, boundary,
                   levels, self._flags(flags, dev), self._ptr(det, dev), self._ptr(app, dev)))
@@ -199,6 +213,12 @@ class Engine:
         one = len(shape) == 1
         B, N = (1, shape[0]) if one else shape
         y = self._empty(ra, dev, shape)
+        if len(lo) != len(hi):  # a biorthogonal bank: the synthesis pair (vw_modwt_inverse_bi_*)
+            fn = self.lib.vw_modwt_inverse_bi_f32 if f32 else self.lib.vw_modwt_inverse_bi_f64
+            _check(fn(self.ctx, dp, ap, B, N, nat.taps_array(lo), len(lo), nat.taps_array(hi), len(hi), wavelet_id,
+                      boundary, levels, detail_mask & 0xFFFFFFFF, 1 if approx_zero else 0, self._flags(flags, dev),
+                      self._ptr(y, dev)))
+            return y
         fn = self.lib.vw_modwt_inverse_f32 if f32 else self.lib.vw_modwt_inverse_f64
         _check(fn(self.ctx, dp, ap, B, N, nat.taps_array(lo), nat.taps_array(hi), len(lo), wavelet_id, boundary, levels,
                   detail_mask & 0xFFFFFFFF, 1 if approx_zero else 0, self._flags(flags, dev), self._ptr(y, dev)))
@@ -210,6 +230,11 @@ class Engine:
         B, N = (1, xa.shape[0]) if one else xa.shape
         app = self._empty(xa, dev, xa.shape)
         det = self._empty(xa, dev, xa.shape)
+        if len(lo) != len(hi):
+            _check(self.lib.vw_modwt1_forward_bi_f64(self.ctx, xp, B, N, N, nat.taps_array(lo), len(lo),
+                                                     nat.taps_array(hi), len(hi), boundary, self._flags(flags, dev),
+                                                     self._ptr(app, dev), self._ptr(det, dev)))
+            return app, det
         _check(self.lib.vw_modwt1_forward_f64(self.ctx, xp, B, N, N, nat.taps_array(lo), nat.taps_array(hi), len(lo),
                                               boundary, self._flags(flags, dev), self._ptr(app, dev),
                                               self._ptr(det, dev)))
@@ -221,6 +246,11 @@ class Engine:
         one = aa.ndim == 1
         B, N = (1, aa.shape[0]) if one else aa.shape
         y = self._empty(aa, dev, aa.shape)
+        if len(lo) != len(hi):
+            _check(self.lib.vw_modwt1_inverse_bi_f64(self.ctx, ap, dp, B, N, nat.taps_array(lo), len(lo),
+                                                     nat.taps_array(hi), len(hi), boundary, self._flags(flags, dev),
+                                                     self._ptr(y, dev)))
+            return y
         _check(self.lib.vw_modwt1_inverse_f64(self.ctx, ap, dp, B, N, nat.taps_array(lo), nat.taps_array(hi), len(lo),
                                               boundary, self._flags(flags, dev), self._ptr(y, dev)))
         return y
@@ -232,7 +262,8 @@ class Engine:
         B, N = (1, xa.shape[0]) if one else xa.shape
         y = self._empty(xa, dev, xa.shape)
         thr = self._empty(xa, dev, (B,)) if want_thresholds else None
-        _check(self.lib.vw_swt_denoise_f64(self.ctx, xp, B, N, N, nat.taps_array(lo), nat.taps_array(hi), len(lo),
+        _check(self.lib.vw_swt_denoise_f64(self.ctx, xp, B, N, N, nat.taps_array(lo), nat.taps_array(hi),
+                                           _one_length(lo, hi, "denoise"),
                                            wavelet_id, boundary, levels, float(threshold), 1 if soft else 0,
                                            self._flags(flags, dev), self._ptr(y, dev), self._ptr(thr, dev)))
         return (y, thr) if want_thresholds else y
@@ -245,7 +276,8 @@ class Engine:
         B, N = (1, xa.shape[0]) if one else xa.shape
         y = self._empty(xa, dev, xa.shape)
         thr = self._empty(xa, dev, (max(levels, 1), B)) if want_thresholds else None
-        _check(self.lib.vw_wavelet_denoise_f64(self.ctx, xp, B, N, N, nat.taps_array(lo), nat.taps_array(hi), len(lo),
+        _check(self.lib.vw_wavelet_denoise_f64(self.ctx, xp, B, N, N, nat.taps_array(lo), nat.taps_array(hi),
+                                               _one_length(lo, hi, "wavelet_denoise"),
                                                wavelet_id, boundary, levels, method, float(fixed), 1 if soft else 0,
                                                self._flags(flags, dev), self._ptr(y, dev), self._ptr(thr, dev)))
         return (y, thr) if want_thresholds else y
@@ -266,7 +298,8 @@ class Engine:
         detail std).  ``N``: row length when the array is wider (its width is the leading dimension)."""
         xa, dev, xp, B, n, ld = self._rows(prices, N)
         out = self._empty(xa, dev, (5, B))
-        _check(self.lib.vw_fin_analyze_f64(self.ctx, xp, B, n, ld, nat.taps_array(lo), nat.taps_array(hi), len(lo),
+        _check(self.lib.vw_fin_analyze_f64(self.ctx, xp, B, n, ld, nat.taps_array(lo), nat.taps_array(hi),
+                                           _one_length(lo, hi, "fin_analyze"),
                                            float(anomaly_k), self._flags(flags, dev), self._ptr(out, dev)))
         return out
 
@@ -284,8 +317,8 @@ class Engine:
         xa, dev, xp, B, n, ld = self._rows(returns, N)
         out = self._empty(xa, dev, (B,))
         _check(self.lib.vw_fin_wavelet_sharpe_f64(self.ctx, xp, B, n, ld, nat.taps_array(lo), nat.taps_array(hi),
-                                                  len(lo), int(boundary), float(risk_free),
-                                                  self._flags(flags, dev), self._ptr(out, dev)))
+                                                  _one_length(lo, hi, "fin_wavelet_sharpe"), int(boundary),
+                                                  float(risk_free), self._flags(flags, dev), self._ptr(out, dev)))
         return out
 
     # -- wavelet energy per level (vw_modwt_energy_f64 / vw_energy_planes_f64) ---------------------
@@ -297,7 +330,8 @@ class Engine:
         LDS).  ``N``: row length when the array is wider (its width is the leading dimension)."""
         xa, dev, xp, B, n, ld = self._rows(x, N)
         out = self._empty(xa, dev, (levels + 1, B))
-        _check(self.lib.vw_modwt_energy_f64(self.ctx, xp, B, n, ld, nat.taps_array(lo), nat.taps_array(hi), len(lo),
+        _check(self.lib.vw_modwt_energy_f64(self.ctx, xp, B, n, ld, nat.taps_array(lo), nat.taps_array(hi),
+                                            _one_length(lo, hi, "energy"),
                                             wavelet_id, boundary, levels, self._flags(flags, dev),
                                             self._ptr(out, dev)))
         return out

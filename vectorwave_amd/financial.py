@@ -20,7 +20,7 @@ import numpy as np
 from . import _native as nat
 from .errors import InvalidStateException
 from .modwt import BoundaryMode, MODWTTransform, _engine_for
-from .wavelets import Daubechies, Haar
+from .wavelets import Daubechies, Haar, require_orthogonal
 
 
 def _java_double(v: float) -> str:
@@ -181,6 +181,7 @@ class FinancialAnalyzer:
         if not hasattr(prices, "shape"):
             prices = np.asarray(prices, dtype=np.float64)
         w = self._wavelet
+        require_orthogonal(w, "FinancialAnalyzer")
         flags = (nat.FLAG_VALIDATE if validate else 0) | (nat.FLAG_TREE_SUMS if tree_sums else 0)
         return _engine_for(prices).fin_analyze(prices, w.lowPassDecomposition(), w.highPassDecomposition(),
                                                self._config.getAnomalyDetectionThreshold(), flags)
@@ -264,6 +265,7 @@ class FinancialWaveletAnalyzer:
         returns = self._returns(returns)
         t = self._transform
         w = t.getWavelet()
+        require_orthogonal(w, "FinancialWaveletAnalyzer.calculateWaveletSharpeRatio")
         flags = (nat.FLAG_VALIDATE if validate else 0) | (nat.FLAG_TREE_SUMS if tree_sums else 0)
         return _engine_for(returns).fin_wavelet_sharpe(returns, w.lowPassDecomposition(), w.highPassDecomposition(),
                                                        int(t.getBoundaryMode()), self._rf(riskFreeRate), flags)

@@ -17,7 +17,7 @@ import numpy as np
 from . import _native as nat
 from .engine import Engine, _is_device_tensor, max_levels as _max_levels
 from .errors import ErrorCode, InvalidArgumentException, InvalidSignalException
-from .wavelets import Wavelet
+from .wavelets import Wavelet, require_orthogonal
 
 try:
     import torch
@@ -368,6 +368,7 @@ class MultiLevelMODWTTransform:
         getRelativeEnergyDistribution's [approx, d1..dJ] order (signals [B, N], or [N] with B = 1).  Default: the
         reference's decompose + computeEnergy bit for bit (sequential sums); ``tree_sums``: tree reductions,
         fused with the forward where its cascade fits."""
+        require_orthogonal(self.wavelet, "MultiLevelMODWTTransform.energyBatch")
         _validate_signal(signals)
         if levels is None:
             levels = self.getMaximumLevels(_length(signals))

@@ -28,7 +28,7 @@ from . import _native as nat
 from .engine import Engine, _check
 from .errors import InvalidArgumentException
 from .shard import shard_rows
-from .wavelets import Wavelet
+from .wavelets import Wavelet, require_orthogonal
 
 
 class DeviceGroup:
@@ -55,6 +55,7 @@ class DeviceGroup:
                 core_levels: bool = False):
         """x [B][N] host -> (details [J][B][N], approx [B][N]) host (BatchMODWT.multiLevelAoS semantics;
         ``core_levels``: MultiLevelMODWTTransform's level cap)."""
+        require_orthogonal(wavelet, "DeviceGroup.forward")
         a = np.ascontiguousarray(np.asarray(x, dtype=np.float64))
         if a.ndim != 2 or a.shape[0] == 0 or a.shape[1] == 0:
             raise InvalidArgumentException("signals must be a non-empty [batch][length] array")
@@ -72,6 +73,7 @@ class DeviceGroup:
 
     def inverse(self, details, approx, wavelet: Wavelet, boundary: int = nat.PERIODIC, fma: bool = False):
         """details [J][B][N], approx [B][N] host -> y [B][N] host (MultiLevelMODWTTransform.reconstruct)."""
+        require_orthogonal(wavelet, "DeviceGroup.inverse")
         d = np.ascontiguousarray(np.asarray(details, dtype=np.float64))
         ap = np.ascontiguousarray(np.asarray(approx, dtype=np.float64))
         if d.ndim != 3 or tuple(d.shape[1:]) != tuple(ap.shape):
@@ -101,6 +103,7 @@ class DeviceGroup:
         sharded across GPUs) -> [(details [J][B_k][N], approx [B_k][N])], allocated on the same devices.
         One ``vw_modwt_forward_multi_dev_f64`` call: context k's host thread enqueues its shard on its own
         stream, nothing crosses PCIe; returns when every shard is done."""
+        require_orthogonal(wavelet, "DeviceGroup.forward_device")
         import torch
         if len(xs) != len(self.engines):
             raise InvalidArgumentException("one tensor per context")
@@ -125,6 +128,7 @@ class DeviceGroup:
 
     def inverse_device(self, parts, wavelet: Wavelet, boundary: int = nat.PERIODIC, fma: bool = False):
         """parts: [(details [J][B_k][N], approx [B_k][N])] per context, on its device -> [y [B_k][N]]."""
+        require_orthogonal(wavelet, "DeviceGroup.inverse_device")
         import torch
         if len(parts) != len(self.engines):
             raise InvalidArgumentException("one (details, approx) pair per context")

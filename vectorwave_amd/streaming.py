@@ -19,7 +19,7 @@ import numpy as np
 from . import _native as nat
 from .errors import InvalidArgumentException, InvalidSignalException, InvalidStateException
 from .modwt import BoundaryMode, MODWTResult, MultiLevelMODWTTransform, _check_boundary, _engine_for
-from .wavelets import Wavelet
+from .wavelets import Wavelet, require_orthogonal
 
 
 class StreamingStatistics:
@@ -98,6 +98,7 @@ class _StreamBase(_Publisher):
             raise InvalidArgumentException("Boundary mode cannot be null")
         if bufferSize <= 0:
             raise InvalidArgumentException(f"Buffer size must be positive, got: {bufferSize}")
+        require_orthogonal(wavelet, "streaming MODWT")
         _check_boundary(BoundaryMode(boundaryMode))
         self.wavelet = wavelet
         self.boundaryMode = BoundaryMode(boundaryMode)
@@ -340,6 +341,7 @@ class MODWTStreamingDenoiser:
         from .engine import Engine
         from .modwt import MODWTTransform
         self._torch = torch
+        require_orthogonal(b._wavelet, "MODWTStreamingDenoiser")
         self.transform = MODWTTransform(b._wavelet, b._boundary)
         self.denoiser = WaveletDenoiser(b._wavelet, b._boundary)
         self.bufferSize = b._bufferSize

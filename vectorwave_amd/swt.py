@@ -11,7 +11,7 @@ from .engine import Engine, _is_device_tensor
 from .errors import ErrorCode, InvalidSignalException
 from .modwt import (BoundaryMode, MultiLevelMODWTTransform, MutableMultiLevelMODWTResult, _check_boundary,
                     _engine_for, _length)
-from .wavelets import Wavelet
+from .wavelets import Wavelet, require_orthogonal
 
 try:
     import torch
@@ -113,6 +113,7 @@ class VectorWaveSwtAdapter:
         if _length(signal) == 0:
             raise InvalidSignalException("Signal cannot be empty for SWT", ErrorCode.VAL_EMPTY)
         w = self.wavelet
+        require_orthogonal(w, "VectorWaveSwtAdapter.denoise")
         flags = self._forward_flags(_length(signal), levels)
         return _engine_for(signal).denoise(signal, w.lowPassDecomposition(), w.highPassDecomposition(), w.wavelet_id,
                                            int(self.boundaryMode), levels, threshold, soft, flags,

@@ -205,11 +205,165 @@ class Coiflet:
     COIF5 = Wavelet("coif5", _COIF5, WID_COIF5, vanishing_moments=10)
 
 
+class BiorthogonalWavelet(Wavelet):
+    """A biorthogonal bank (core/api/BiorthogonalSpline.java:304-339): the two stored low-pass filters, NOT
+    normalised, and the high-pass filters derived from the other side's low-pass,
+
+        highPassDecomposition[i]  = sign * lowPassRecon[n-1-i]
+        highPassReconstruction[i] = sign * lowPassDecomp[n-1-i],   sign = +1 when (n-1-i) is even, else -1
+
+    (for even n the opposite of the orthogonal QMF sign ``(-1)^i``).  The analysis pair has lengths
+    (len(dec), len(rec)), the synthesis pair (len(rec), len(dec)).  ``filter_length`` is the decomposition
+    low-pass length; ``wavelet_id`` is WID_OTHER (SymmetricAlignmentStrategy knows none of these objects).
+    reconstructionScale / groupDelay are used by no MODWT code and are not carried."""
+
+    def __init__(self, name: str, low_dec: Tuple[float, ...], low_rec: Tuple[float, ...],
+                 vanishing_moments: int = 0, dual_vanishing_moments: int = 0):
+        self._name = name
+        self._low = tuple(float(v) for v in low_dec)
+        self._low_rec = tuple(float(v) for v in low_rec)
+        self._high = self._mirror(self._low_rec)
+        self._high_rec = self._mirror(self._low)
+        self.wavelet_id = WID_OTHER
+        self._vm = vanishing_moments
+        self._dvm = dual_vanishing_moments
+
+    @staticmethod
+    def _mirror(h: Tuple[float, ...]) -> Tuple[float, ...]:
+        n = len(h)
+        return tuple((1 if (n - 1 - i) % 2 == 0 else -1) * h[n - 1 - i] for i in range(n))
+
+    def lowPassReconstruction(self):
+        return list(self._low_rec)
+
+    def highPassReconstruction(self):
+        return list(self._high_rec)
+
+    def dualVanishingMoments(self) -> int:
+        return self._dvm
+
+    def reversed(self, name: str) -> "BiorthogonalWavelet":
+        """ReverseBiorthogonalSpline.java:107-128: the decomposition and reconstruction roles swapped."""
+        return BiorthogonalWavelet(name, self._low_rec, self._low, self._dvm, self._vm)
+
+    def __repr__(self) -> str:
+        return f"BiorthogonalWavelet({self._name}, dec {len(self._low)}/{len(self._high)})"
+
+
+def is_biorthogonal(w) -> bool:
+    """True when the wavelet's decomposition and reconstruction filters differ: the calls whose ABI takes one
+    filter pair for both directions cannot run it."""
+    return (list(w.lowPassDecomposition()) != list(w.lowPassReconstruction())
+            or list(w.highPassDecomposition()) != list(w.highPassReconstruction()))
+
+
+def require_orthogonal(w, what: str) -> None:
+    """Raise (before any launch) where a path takes ONE filter pair for both directions."""
+    if is_biorthogonal(w):
+        raise NotImplementedError(  # VW_ERR_UNSUPPORTED's exception type (errors.raise_for_status)
+            f"{what} does not support the biorthogonal wavelet {w.name()!r}: its decomposition and reconstruction "
+            f"filters differ and this path takes one filter pair for both directions")
+
+
+# BiorthogonalSpline.java:20-28, computed the way Java computes them
+_ONE_EIGHTH = 1.0 / 8.0
+_S2I = 1.0 / math.sqrt(2.0)
+_HALF_S2I = 0.5 / math.sqrt(2.0)
+_QUARTER_S2I = 0.25 / math.sqrt(2.0)
+_THREE_QUARTER_S2I = 0.75 / math.sqrt(2.0)
+_THREE_HALF_S2I = 1.5 / math.sqrt(2.0)
+_REC2 = (_HALF_S2I, _S2I, _HALF_S2I)
+_REC3 = (_QUARTER_S2I, _THREE_QUARTER_S2I, _THREE_QUARTER_S2I, _QUARTER_S2I)
+
+
+class BiorthogonalSpline:
+    """core/api/BiorthogonalSpline.java:30-267 (biorNr.Nd: reconstruction order Nr, decomposition order Nd)."""
+
+    BIOR1_1 = BiorthogonalWavelet("bior1.1", (_S2I, _S2I), (_S2I, _S2I), 1, 1)
+    BIOR1_3 = BiorthogonalWavelet(
+        "bior1.3", (-1.0 / 8.0, _ONE_EIGHTH, 1.0, 1.0, _ONE_EIGHTH, -1.0 / 8.0), (1.0, 1.0), 3, 1)
+    BIOR1_5 = BiorthogonalWavelet("bior1.5", (
+        0.016387336463, -0.041464936782, -0.067372554722, 0.386110066823,
+        0.812723635450, 0.417005184424, -0.076488599078, -0.059434418646,
+        0.023680171947, 0.005611434819), (_S2I, _S2I), 5, 1)
+    BIOR2_2 = BiorthogonalWavelet(
+        "bior2.2", (-_QUARTER_S2I, _HALF_S2I, _THREE_HALF_S2I, _HALF_S2I, -_QUARTER_S2I), _REC2, 2, 2)
+    BIOR2_4 = BiorthogonalWavelet("bior2.4", (
+        0.03782845550726, -0.02384946501956, -0.11062440441844, 0.37740285561138,
+        0.85269867900889, 0.37740285561138, -0.11062440441844, -0.02384946501956,
+        0.03782845550726), _REC2, 4, 2)
+    BIOR2_6 = BiorthogonalWavelet("bior2.6", (
+        -0.00679744371334, 0.00193588752085, 0.03307121615827, -0.06650878107113,
+        -0.17185392490960, 0.42063224422510, 0.99438208967163, 0.42063224422510,
+        -0.17185392490960, -0.06650878107113, 0.03307121615827, 0.00193588752085,
+        -0.00679744371334), _REC2, 6, 2)
+    BIOR2_8 = BiorthogonalWavelet("bior2.8", (
+        0.00133639669065, 0.00020703315896, -0.00750912736790, 0.00513451063436,
+        0.03968708834741, -0.05514273381420, -0.15999329944587, 0.29774790265169,
+        1.13158823408280, 0.29774790265169, -0.15999329944587, -0.05514273381420,
+        0.03968708834741, 0.00513451063436, -0.00750912736790, 0.00020703315896,
+        0.00133639669065), _REC2, 8, 2)
+    BIOR3_1 = BiorthogonalWavelet(
+        "bior3.1", (-_HALF_S2I, _THREE_HALF_S2I, _THREE_HALF_S2I, -_HALF_S2I), _REC3, 1, 3)
+    BIOR3_3 = BiorthogonalWavelet("bior3.3", (
+        0.06629126073624, -0.19887378220871, -0.15467960838456, 0.99436891104358,
+        0.99436891104358, -0.15467960838456, -0.19887378220871, 0.06629126073624), _REC3, 3, 3)
+    BIOR3_5 = BiorthogonalWavelet("bior3.5", (
+        -0.01380930374353, 0.04145791438182, 0.05224175305576, -0.26792357880567,
+        -0.07181553374457, 0.96674755240348, 0.96674755240348, -0.07181553374457,
+        -0.26792357880567, 0.05224175305576, 0.04145791438182, -0.01380930374353), _REC3, 5, 3)
+    BIOR3_7 = BiorthogonalWavelet("bior3.7", (
+        0.00353713800152, -0.00709427600303, -0.00881784307093, 0.06207776192089,
+        0.00123255138768, -0.24072663312710, 0.03892321448596, 0.97875960941423,
+        0.97875960941423, 0.03892321448596, -0.24072663312710, 0.00123255138768,
+        0.06207776192089, -0.00881784307093, -0.00709427600303, 0.00353713800152), _REC3, 7, 3)
+    BIOR3_9 = BiorthogonalWavelet("bior3.9", (
+        -0.00088388347648, 0.00141682627301, 0.00294786709734, -0.01721018024336,
+        -0.00471408733933, 0.06375562764545, -0.01636499682386, -0.17520070369698,
+        0.11175187708906, 1.01284028851077, 1.01284028851077, 0.11175187708906,
+        -0.17520070369698, -0.01636499682386, 0.06375562764545, -0.00471408733933,
+        -0.01721018024336, 0.00294786709734, 0.00141682627301, -0.00088388347648), _REC3, 9, 3)
+    BIOR4_4 = BiorthogonalWavelet("bior4.4", (
+        0.03782845550699, -0.02384946501938, -0.11062440441842, 0.37740285561265,
+        0.85269867900940, 0.37740285561265, -0.11062440441842, -0.02384946501938,
+        0.03782845550699), (
+        -0.06453888262876, -0.04068941760916, 0.41809227322162, 0.78848561640558,
+        0.41809227322162, -0.04068941760916, -0.06453888262876), 4, 4)
+    BIOR5_5 = BiorthogonalWavelet("bior5.5", (
+        0.01388101643146, -0.04166303571439, -0.06739205471574, 0.38611006682117,
+        0.81272363544987, 0.41700518442165, -0.07648488313481, -0.05943441806447,
+        0.02368017193823, 0.00561143481953, -0.00182320886991, -0.00071799821619), (
+        -0.01514974064694, -0.01514974064694, 0.30298948129389, 0.60597896258778,
+        0.60597896258778, 0.30298948129389, -0.01514974064694, -0.01514974064694), 5, 5)
+    BIOR6_8 = BiorthogonalWavelet("bior6.8", (
+        0.00199043589843, 0.00033522297333, -0.01259715653306, 0.00620544193220,
+        0.06776863310747, -0.08602163816209, -0.31275875600911, 0.22783840537710,
+        1.35158010213994, 0.22783840537710, -0.31275875600911, -0.08602163816209,
+        0.06776863310747, 0.00620544193220, -0.01259715653306, 0.00033522297333,
+        0.00199043589843), (
+        0.00044174303816, -0.00132354366062, -0.00048809535103, 0.01141610211580,
+        -0.01159170830368, -0.03158210553249, 0.14270775786152, 0.72656452844835,
+        0.72656452844835, 0.14270775786152, -0.03158210553249, -0.01159170830368,
+        0.01141610211580, -0.00048809535103, -0.00132354366062, 0.00044174303816), 8, 6)
+
+
+class ReverseBiorthogonalSpline:
+    """core/api/ReverseBiorthogonalSpline.java:26-128: RBIOx_y is BIORx_y with the two sides swapped."""
+
+
+for _k, _v in list(vars(BiorthogonalSpline).items()):
+    if isinstance(_v, BiorthogonalWavelet):
+        setattr(ReverseBiorthogonalSpline, "RBIO" + _k[4:], _v.reversed("rbio" + _v.name()[4:]))
+
 _REGISTRY: Dict[str, Wavelet] = {"haar": Haar.INSTANCE}
 for _cls in (Daubechies, Symlet, Coiflet):
     for _k, _v in vars(_cls).items():
         if isinstance(_v, Wavelet):
             _REGISTRY[_k.lower()] = _v
+for _cls in (BiorthogonalSpline, ReverseBiorthogonalSpline):  # under the reference's names: bior4.4, rbio2.2, ...
+    for _k, _v in vars(_cls).items():
+        if isinstance(_v, BiorthogonalWavelet):
+            _REGISTRY[_v.name()] = _v
 
 
 def get_wavelet(name: str) -> Wavelet:
