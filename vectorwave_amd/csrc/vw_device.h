@@ -812,8 +812,10 @@ __device__ __forceinline__ void zero_regs(T (&r)[NV][VT<T>::V]) {
 
 // Launch bounds of the fused kernels.  NV = 4: at most 512 threads and W waves per SIMD -- W = 8
 // (64 VGPRs: four 512-thread workgroups per CU, LDS permitting) for the forward, W = 6 (80 VGPRs,
-// three workgroups) for the inverse, whose prefetched detail row occupies 16 more VGPRs -- so
-// several workgroups share a CU and hide each other's barriers and row loads.  NV = 8 (long
+// three workgroups) for the inverses, whose prefetched detail row occupies 16 more VGPRs -- so
+// several workgroups share a CU and hide each other's barriers and row loads.  The one inverse that
+// also exists at W = 8 is k_inverse_seq's PLAIN form (fp64, L <= 8; inverse_seq_plain): it fits 64 VGPRs
+// without scratch, and VW_INV_WAVES picks between its two instantiations.  NV = 8 (long
 // signals): up to 1024 threads, 128 VGPRs.
 // Longer filters need wider register windows (the s = 1 window holds L + V - 1 values): L <= 8 gets
 // W waves, longer filters 4 (128 VGPRs; with 512-thread workgroups 5 waves would not add one).
@@ -1235,13 +1237,178 @@ __global__ void VW_FUSED_BOUNDS(NV, VW_FUSED_W((L > LH ? L : LH), 6)) k_inverse_
 // Single-buffer sequential-sum form for signals too long for two LDS buffers: ONE region is
 // time-shared (a_j -> approx branch -> d_j -> detail branch -> a_{j-1}); four barriers per level.
 #ifndef VW_INV_W
-#define VW_INV_W 6  // waves per SIMD of k_inverse_seq (experiment builds: -DVW_INV_W=8 -> 64 VGPRs)
+#define VW_INV_W 6  // waves per SIMD of k_inverse_seq's general forms (the PLAIN form names its own: W below)
 #endif
+// ---- PLAIN form of the full-slab kernel -----------------------------------------------------------
+// A PERIODIC reconstruction from all of its coefficients (host: InvArgs::plain): every level reads t + i*s, so
+// there is no left halo and the right one is the row's first hr elements again; no threshold, no zeroed
+// level, no probe, forward walk.  What the general form carries for those cases -- the level descriptor, the
+// threshold pointer and stride, the modulo of the generic halo fill, 64-bit flat addresses per lane and
+// vector -- is never live here, and that is what lets the kernel fit 64 VGPRs (four 512-thread workgroups
+// per CU) without scratch.  The one per-lane address is the byte offset vb = (tid + k * NT) * 16 of a vector
+// in its row, the same for global rows (raw buffer instructions: the row base is an SGPR resource) and LDS.
+// Per output: the same LDS values, taps ascending, approximation branch then detail branch, the same
+// multiply / add instructions as the general form -- bit-identical results.
+template <int NV, typename F>
+__device__ __forceinline__ void plain_vecs(unsigned slab, F&& fn) {
+#pragma unroll
+  for (int k = 0; k < NV; ++k) {
+    unsigned vb = threadIdx.x * 16u;
+    asm volatile("" : "+v"(vb));  // only tid * 16 stays live across the level loop (see for_vecs)
+    fn(k, vb + k * slab);
+    __builtin_amdgcn_sched_barrier(0);  // one vector's LDS reads at a time (see for_vecs)
+  }
+}
+
+// Row <-> registers; non-temporal (aux 2), as the general form's flat loads and stores.
+template <typename T, int NV>
+__device__ __forceinline__ void plain_load_row(T (&r)[NV][VT<T>::V], const T* row, unsigned slab) {
+  using vec = typename VT<T>::v;
+  const __amdgpu_buffer_rsrc_t rs = row_rsrc(row);
+  unsigned vb = threadIdx.x * 16u;
+  asm volatile("" : "+v"(vb));
+#pragma unroll
+  for (int k = 0; k < NV; ++k) {  // loads only: first touched where they are written to LDS (load_row_regs)
+    const vec v = __builtin_bit_cast(vec, __builtin_amdgcn_raw_buffer_load_b128(rs, vb, k * slab, 2));
+#pragma unroll
+    for (int e = 0; e < VT<T>::V; ++e) r[k][e] = v[e];
+  }
+}
+template <typename T, int NV>
+__device__ __forceinline__ void plain_store_row(T* row, const T (&r)[NV][VT<T>::V], unsigned slab) {
+  using vec = typename VT<T>::v;
+  const __amdgpu_buffer_rsrc_t rs = row_rsrc(row);
+  unsigned vb = threadIdx.x * 16u;
+  asm volatile("" : "+v"(vb));
+#pragma unroll
+  for (int k = 0; k < NV; ++k) {
+    vec o;
+#pragma unroll
+    for (int e = 0; e < VT<T>::V; ++e) o[e] = r[k][e];
+    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(vw_i4, o), rs, vb, k * slab, 2);
+  }
+}
+
+// Registers -> LDS level buffer with its right halo [N, N + hr): by the owners of elements [0, hr) where they
+// all sit in the first slab (own; regs_to_level_m), else copied after a barrier (hr <= N: host contract).
+template <typename T, int NV>
+__device__ __forceinline__ void plain_to_level(T* R, const T (&r)[NV][VT<T>::V], unsigned slab, int N, int hr, int own) {
+  constexpr int V = VT<T>::V;
+  using vec = typename VT<T>::v;
+  plain_vecs<NV>(slab, [&](int k, unsigned vb) {
+    vec o;
+#pragma unroll
+    for (int e = 0; e < V; ++e) o[e] = r[k][e];
+    T* const at = reinterpret_cast<T*>(reinterpret_cast<unsigned char*>(R) + vb);
+    *reinterpret_cast<vec*>(at) = o;
+    if (k == 0 && own && vb < (unsigned)hr * (unsigned)sizeof(T)) {
+#pragma unroll
+      for (int e = 0; e < V; ++e)
+        if (vb + e * (unsigned)sizeof(T) < (unsigned)hr * (unsigned)sizeof(T)) at[N + e] = o[e];
+    }
+  });
+  if (!own) {
+    lds_barrier();
+    for (int q = threadIdx.x; q < hr; q += blockDim.x) R[N + q] = R[q];
+  }
+}
+
+// One branch over the row: acc[k]_e (+)= f[i] * R[t0 + e + i*s], i ascending (inv_row_t / inv_row_ct at
+// dir = +1, off = 0).  S > 0: compile-time spacing, one base and immediate offsets; S = 0: run-time spacing;
+// S < 0: the register window of spacing -S (below the vector width).  RIF: LDS reads in flight per vector.
+template <typename T, int L, bool FMA, int NV, int RIF, int S>
+__device__ __forceinline__ void plain_row_s(const T* R, unsigned slab, int s, const T* f, T (&acc)[NV][VT<T>::V]) {
+  constexpr int V = VT<T>::V;
+  using vec = typename VT<T>::v;
+  plain_vecs<NV>(slab, [&](int k, unsigned vb) {
+    const T* const at = reinterpret_cast<const T*>(reinterpret_cast<const unsigned char*>(R) + vb);
+    if constexpr (S < 0) {
+      inv_window<T, L, FMA, -S, 1>(at, 0, f, acc[k]);
+    } else {
+      const unsigned a0 = lds_base(at);
+#pragma unroll
+      for (int i = 0; i < L; ++i) {
+        const vec v = S > 0 ? lds_vec_at<vec>(a0 + (unsigned)(i * S * (int)sizeof(T)))
+                            : *reinterpret_cast<const vec*>(at + i * s);
+        vmadd<FMA>(acc[k], v, f[i]);
+        if (i % RIF == RIF - 1) __builtin_amdgcn_sched_barrier(0);  // <= RIF reads in flight (VGPR budget)
+      }
+    }
+#pragma unroll
+    for (int e = 0; e < V; ++e) asm volatile("" : "+v"(acc[k][e]));  // pin the sums here (see inv_row_t)
+  });
+}
+template <typename T, int L, bool FMA, int NV, int RIF>
+__device__ __forceinline__ void plain_row(const T* R, unsigned slab, int s, const T* f, T (&acc)[NV][VT<T>::V]) {
+  constexpr int V = VT<T>::V;
+  if (s == 1) return plain_row_s<T, L, FMA, NV, RIF, -1>(R, slab, s, f, acc);
+  if constexpr (V == 4) {
+    if (s == 2) return plain_row_s<T, L, FMA, NV, RIF, -2>(R, slab, s, f, acc);
+  }
+  switch (s) {  // the spacing dispatched once per row, level and branch (inv_row)
+#define VW_CASE(n)                                                                             \
+    case n:                                                                                    \
+      if constexpr (n % V == 0) return plain_row_s<T, L, FMA, NV, RIF, n>(R, slab, s, f, acc); \
+      break;
+    VW_CT_SPACINGS(VW_CASE)
+#undef VW_CASE
+    default: break;
+  }
+  plain_row_s<T, L, FMA, NV, RIF, 0>(R, slab, s, f, acc);
+}
+
+// k_inverse_seq's schedule (below), phase for phase; a level reads only its spacing, right halo and owner flag.
+// W = 8 keeps three LDS reads in flight per output vector where the general form and W = 6 keep four: with
+// the detail-row prefetch (16 VGPRs) and both sums live that is what 64 VGPRs hold.
+template <typename T, int L, bool FMA, int NV, int W>
+__device__ __forceinline__ void inverse_seq_plain(const InvArgs<T>& p) {
+  constexpr int V = VT<T>::V;
+  constexpr int RIF = W >= 8 ? 3 : 4;
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  T* const R = reinterpret_cast<T*>(smem) + p.hlpad_a;
+  const size_t N = (size_t)p.N;
+  const size_t row = (size_t)blockIdx.x * N, plane = (size_t)p.B * N;
+  const unsigned slab = blockDim.x * 16u;  // bytes between a lane's vectors
+
+  T acc[NV][V];
+  T dreg[NV][V];
+  plain_load_row<T, NV>(acc, p.approx + row, slab);
+  plain_load_row<T, NV>(dreg, p.details + (size_t)(p.J - 1) * plane + row, slab);
+  wait_vmem();
+  plain_to_level<T, NV>(R, acc, slab, p.N, p.lv[p.J - 1].hr, p.lv[p.J - 1].own);
+
+  for (int j = p.J; j >= 1; --j) {
+    const int s = p.lv[j - 1].s;
+    lds_barrier();  // R = a_j + halo
+    zero_regs<T, NV>(acc);
+    plain_row<T, L, FMA, NV, RIF>(R, slab, s, p.lo, acc);
+    lds_barrier();  // every approximation-branch read done
+    wait_vmem();    // the d_j prefetch
+    plain_to_level<T, NV>(R, dreg, slab, p.N, p.lv[j - 1].hr, p.lv[j - 1].own);
+    if (j > 1)  // the d_{j-1} prefetch, in flight across the detail branch
+      plain_load_row<T, NV>(dreg, p.details + (size_t)(j - 2) * plane + row, slab);
+    lds_barrier();  // R = d_j + halo
+    plain_row<T, L, FMA, NV, RIF>(R, slab, s, p.hi, acc);
+    if (j > 1) {
+      lds_barrier();  // every detail-branch read done
+      plain_to_level<T, NV>(R, acc, slab, p.N, p.lv[j - 2].hr, p.lv[j - 2].own);
+    }
+  }
+  plain_store_row<T, NV>(p.y + row, acc, slab);
+}
+
 // FULL: aligned rows with every slab full (threads * NV == N / V; host: InvArgs::full) -- the bounds
 // checks of the row transfers and the ragged-row store path are compiled out (VW_LEVEL_CT).
 // LH: as k_inverse_db.
-template <typename T, int L, bool FMA, int NV, bool FULL = false, int LH = L>
-__global__ void VW_FUSED_BOUNDS(NV, VW_FUSED_W((L > LH ? L : LH), VW_INV_W)) k_inverse_seq(const InvArgs<T> p) {
+// W: waves per SIMD the kernel is compiled for (VW_FUSED_BOUNDS).  PLAIN (a FULL form of the short filters):
+// inverse_seq_plain at W = 6 or 8 (host: InvArgs::plain, VW_INV_WAVES).
+template <typename T, int L, bool FMA, int NV, bool FULL = false, int LH = L, int W = VW_INV_W, bool PLAIN = false>
+__global__ void VW_FUSED_BOUNDS(NV, VW_FUSED_W((L > LH ? L : LH), W)) k_inverse_seq(const InvArgs<T> p) {
+  if constexpr (PLAIN) {
+    static_assert(FULL && L > 0 && L <= 8 && LH == L && NV == 4, "the plain form is a full-slab form of the short filters");
+    inverse_seq_plain<T, L, FMA, NV, W>(p);
+    return;
+  }
   constexpr int V = VT<T>::V;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   T* R = reinterpret_cast<T*>(smem) + p.hlpad_a;

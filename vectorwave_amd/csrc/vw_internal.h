@@ -92,6 +92,9 @@ struct InvArgs {
   int unrolled;
   int level_ct;         // 1: compile-time-stride level bodies (VW_LEVEL_CT; vw_device.h inv_row_ct)
   int full;             // 1: aligned rows, threads * NV == N / V: k_inverse_seq's full-slab form may run
+  int plain;            // 1 (with full, fp64): PERIODIC from every coefficient plane -- all levels read t + i*s with
+                        // hr <= N, no threshold, no zeroed plane, no probe, forward walk: k_inverse_seq's PLAIN form
+  int waves;            // waves per SIMD of the PLAIN form's instantiation, 6 or 8 (VW_INV_WAVES)
   int db;               // sequential sum: 1 = two LDS buffers (k_inverse_db), 0 = one (k_inverse_seq)
   int blk;              // 1: register-blocked PERIODIC inverse (k_inverse_blk), padded LDS layouts
   int approx_zero;

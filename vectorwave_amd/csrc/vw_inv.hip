@@ -7,7 +7,7 @@ namespace vw {
 template <typename T, int L, bool FMA, int NV>
 static hipError_t run_inverse_fused_nv(const InvArgs<T>& a, int threads, int lds, hipStream_t st) {
   // pairwise sums: k_inverse_fused; sequential sums: two LDS buffers (k_inverse_db) or one (k_inverse_seq)
-  static LdsOnce configured_pair, configured_seq, configured_db, configured_blk, configured_full;
+  static LdsOnce configured_pair, configured_seq, configured_db, configured_blk, configured_full, configured_plain[2];
   // register-blocked PERIODIC (host contract; never with NV = 2)
   const bool blk = L > 0 && NV != 2 && a.blk && !a.pair && !a.db;
   auto k = a.pair ? k_inverse_fused<T, L, FMA, NV> : a.db ? k_inverse_db<T, L, FMA, NV> : k_inverse_seq<T, L, FMA, NV>;
@@ -20,8 +20,17 @@ static hipError_t run_inverse_fused_nv(const InvArgs<T>& a, int threads, int lds
     full = a.full && !a.pair && !a.db && !blk;
     if (full) k = k_inverse_seq<T, L, FMA, NV, true>;
   }
+  // its PLAIN form (host: InvArgs::plain; the pointers are the executor's), compiled for 6 or 8 waves per SIMD
+  LdsOnce* plain = nullptr;
+  if constexpr (NV == 4 && L > 0 && L <= 8 && std::is_same<T, double>::value) {
+    if (full && a.plain && !a.thr && !a.nf_flag && !a.approx_zero && !a.rev) {
+      const bool w8 = a.waves == 8;
+      k = w8 ? k_inverse_seq<T, L, FMA, NV, true, L, 8, true> : k_inverse_seq<T, L, FMA, NV, true, L, 6, true>;
+      plain = &configured_plain[w8];
+    }
+  }
   hipError_t e = set_lds(k, lds, a.pair ? &configured_pair : a.db ? &configured_db
-                                 : blk ? &configured_blk : full ? &configured_full : &configured_seq);
+                                 : blk ? &configured_blk : plain ? plain : full ? &configured_full : &configured_seq);
   if (e != hipSuccess) return e;
   hipLaunchKernelGGL(k, dim3((unsigned)a.B), dim3(threads), lds, st, a);
   return hipGetLastError();

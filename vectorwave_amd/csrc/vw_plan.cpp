@@ -61,6 +61,7 @@ static const TuningKey kTuningTable[] = {
     VW_KEY("VW_ENERGY_FUSED", t.energy_fused = v < 0 ? d.energy_fused : v),
     VW_KEY("VW_BI", t.bi = v < 0 ? d.bi : v & 7),
     VW_KEY("VW_BI_LISTED", t.bi_listed = v < 0 ? d.bi_listed : v != 0),
+    VW_KEY("VW_INV_WAVES", t.inv_waves = v == 6 || v == 8 ? v : d.inv_waves),
 };
 #undef VW_KEY
 
@@ -881,6 +882,14 @@ static bool plan_inverse_fused(const Tuning& tu, const InvCall<T>& c, bool pair,
   // VW_FLAG_REF_NONFINITE: the one-buffer sequential kernels (k_inverse_seq / k_inverse_blk, vw_inv.hip's
   // choice) probe their output themselves (no scan pass afterwards)
   p->nf_probed = p->ref_nf && (p->kernel == kInvSeq || p->kernel == kInvBlk);
+  // k_inverse_seq's PLAIN form (vw_device.h inverse_seq_plain; fp64 short filters, vw_inv.hip's dispatch): a
+  // full-slab PERIODIC reconstruction that uses none of the general form's optional state
+  bool plain = a.full && p->kernel == kInvSeq && sizeof(T) == 8 && nv == 4 && L <= 8 && periodic && !c.thr &&
+               !c.approx_zero && !a.rev && !p->ref_nf;
+  for (int j = 0; plain && j < J; ++j)
+    plain = a.lv[j].use_d && plus_zero(a.lv[j]) && a.lv[j].hl == 0 && a.lv[j].hr <= N;
+  a.plain = plain ? 1 : 0;
+  a.waves = tu.inv_waves;
   p->threads = threads; p->nv = nv; p->lds = lds;
   return true;
 }
@@ -1067,6 +1076,7 @@ static void plan_inverse_taps(const Tuning& tu, const InvCall<T>& call, int taps
     a.taps = Llo; a.taps_hi = Lhi;
     a.unrolled = a.unrolled && has_unrolled_pair(Llo, Lhi);
     a.full = 0;
+    a.plain = 0;
   }
   if (!p->fused) plan_inverse_levels(tu, c, pair, p);
   reserve_ref<T>(tu, c.cus, c.B, c.N, p);

@@ -68,6 +68,9 @@ struct Tuning {
                                // run each filter at its own tap count where they fit (1 | 2 | 3, as VW_MFMA) and
                                // the pair has compile-time kernels (VW_TAP_PAIR_LIST); bit 2: every other pair too, on
                                // the runtime-L bodies (measured 2-3 x slower than the padded route's unrolled kernels)
+  int inv_waves = 6;           // VW_INV_WAVES=6|8: waves per SIMD k_inverse_seq's PLAIN form is compiled for -- 8 (64 VGPRs)
+                               // lets four 512-thread workgroups share a CU where 6 lets three; measured no
+                               // faster than 6 on the db4 step (profiles/r09/ab_db4_inv_waves.log)
   int bi_listed = 1;           // VW_BI_LISTED=0: a two-length bank runs max(Llo, Lhi) taps even where that count is not in
                                // VW_TAP_LIST (the runtime-L kernels); 1: one more zero tap where that reaches a listed count
 };
