@@ -37,6 +37,8 @@
  *   vw_fin_wavelet_sharpe_* FinancialWaveletAnalyzer.calculateWaveletSharpeRatio  fin/FinancialWaveletAnalyzer.java:166-212
  *   vw_modwt_energy_f64 /   MultiLevelMODWTResult.getDetailEnergyAtLevel / getApproximationEnergy / getTotalEnergy /
  *   vw_energy_planes_f64      getRelativeEnergyDistribution  core/modwt/MultiLevelMODWTResultImpl.java:91-139, :211-216
+ *   vw_mra_planes_* /       VectorWaveSwtAdapter.extractLevel for every level  core/swt/VectorWaveSwtAdapter.java:576-598
+ *   vw_modwt_mra_*            MultiLevelMODWTTransform.reconstructLevels  core/modwt/MultiLevelMODWTTransform.java:398-446
  *   vw_max_levels           MultiLevelMODWTTransform.getMaximumLevels  core/modwt/MultiLevelMODWTTransform.java:455-501, :693-695
  *   status codes            core/exception/ErrorCode.java:24-118 (see the table below)
  *
@@ -289,6 +291,41 @@ VW_API vw_status vw_modwt_energy_f64(vw_ctx *ctx, const double *x, int64_t B, in
                                      int boundary, int J, unsigned flags, double *out);
 VW_API vw_status vw_energy_planes_f64(vw_ctx *ctx, const double *details, const double *approx, int64_t B,
                                       int64_t N, int J, unsigned flags, double *out);
+
+/* ---- multiresolution analysis ----------------------------------------------------------------------
+ * The additive split x = S_J + D_1 + ... + D_J of a MODWT, every component time-aligned to the signal, for a batch
+ * in one call.  out is [J+1][B][N] in getRelativeEnergyDistribution's order: out[0] the smooth (the approximation
+ * alone, every detail zeroed), out[j] detail component j (d_j alone, the approximation zeroed).  Component c is by
+ * definition vw_modwt_inverse_* with detail_mask = c ? 1u << (c-1) : 0 and approx_zero = (c != 0), i.e.
+ * VectorWaveSwtAdapter.extractLevel(signal, J, c) (core/swt/VectorWaveSwtAdapter.java:576-598) /
+ * MultiLevelMODWTTransform.reconstructLevels (core/modwt/MultiLevelMODWTTransform.java:398-446) with one level:
+ * without VW_FLAG_FMA bit for bit that call's result in all three boundary modes.
+ *
+ * vw_mra_planes_* takes coefficient planes (details [J][B][N], approx [B][N]) and makes vw_modwt_inverse_*'s checks
+ * with the same statuses and messages.  Flags: CORE_LEVELS, FMA, HOST_MEMORY, SYNC, VALIDATE, REF_NONFINITE.
+ * vw_modwt_mra_* takes signals: vw_modwt_forward_*'s checks first, then the inverse's; it runs the forward into the
+ * context workspace and the planes call on those coefficients.  VW_FLAG_FFT_SWITCH applies to its forward only.
+ * out must not overlap details, approx or x.  Equal-length banks only.
+ *
+ * Where a row and the longest level's halos fit the GPU's LDS twice, one launch computes all J+1 components and
+ * leaves out the branch passes over zeroed planes (which cannot change a finite sum: the same bits).  That needs
+ * finite data, so with VW_FLAG_VALIDATE or VW_FLAG_REF_NONFINITE -- and for rows that do not fit, for shapes where
+ * that kernel measured slower (long listed filters on aligned rows), or with the context option VW_MRA_FUSED=0 --
+ * the call issues the J+1 masked inverses instead: the same results.  VW_MRA_FUSED=2: the one launch wherever it fits.
+ * Without HOST_MEMORY / VALIDATE / SYNC both calls can be recorded into a vw_graph once a call of that shape has
+ * run (the workspace grows outside a capture only). */
+VW_API vw_status vw_mra_planes_f64(vw_ctx *ctx, const double *details, const double *approx, int64_t B, int64_t N,
+                                   const double *lo, const double *hi, int L, int wavelet_id, int boundary, int J,
+                                   unsigned flags, double *out);
+VW_API vw_status vw_mra_planes_f32(vw_ctx *ctx, const float *details, const float *approx, int64_t B, int64_t N,
+                                   const double *lo, const double *hi, int L, int wavelet_id, int boundary, int J,
+                                   unsigned flags, float *out);
+VW_API vw_status vw_modwt_mra_f64(vw_ctx *ctx, const double *x, int64_t B, int64_t N, int64_t ldx,
+                                  const double *lo, const double *hi, int L, int wavelet_id, int boundary, int J,
+                                  unsigned flags, double *out);
+VW_API vw_status vw_modwt_mra_f32(vw_ctx *ctx, const float *x, int64_t B, int64_t N, int64_t ldx,
+                                  const double *lo, const double *hi, int L, int wavelet_id, int boundary, int J,
+                                  unsigned flags, float *out);
 
 /* ---- one batch over several contexts (one host thread per context) ----------------------------
  * Replaces the reference's in-process parallelism over one batch call: BatchMODWT.multiLevelAoS /

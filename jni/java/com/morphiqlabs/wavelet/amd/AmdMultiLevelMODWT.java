@@ -174,6 +174,64 @@ public final class AmdMultiLevelMODWT {
         return inverse(result, mask, J > maxLevel);
     }
 
+    /**
+     * Multiresolution analysis of a decomposition: {@code [J + 1][N]}, row 0 the smooth
+     * ({@code reconstructLevels}' result with every detail zeroed and the approximation kept), row j detail
+     * component j (only d_j kept, the approximation zeroed) -- what J + 1 calls of the masked inverse give, bit for
+     * bit, from one engine call; the rows add up to {@code reconstruct(result)}.  Like reconstruct* it validates
+     * nothing and carries FLAG_REF_NONFINITE (the engine then loops over the masked inverses);
+     * {@code finite = true} promises finite coefficients and lets the one-launch kernel run.  A
+     * BiorthogonalWavelet loops over the two-length inverse.
+     */
+    public double[][] mra(MultiLevelMODWTResult result, boolean finite) {
+        if (result == null) throw new NullPointerException("result cannot be null");
+        final int J = result.getLevels();
+        final int n = result.getSignalLength();
+        final double[] rlo = wavelet.lowPassReconstruction(), rhi = wavelet.highPassReconstruction();
+        double[][] out = new double[J + 1][];
+        if (rlo.length != rhi.length) {
+            for (int c = 0; c <= J; c++) out[c] = inverse(result, c == 0 ? 0 : 1 << (c - 1), c != 0);
+            return out;
+        }
+        double[][][] d = new double[J][1][];
+        for (int l = 1; l <= J; l++) d[l - 1][0] = result.getDetailCoeffsAtLevel(l);
+        double[][] a = {result.getApproximationCoeffs()};
+        double[] flat = new double[Math.multiplyExact(J + 1, n)];
+        final int flags = AmdNative.FLAG_CORE_LEVELS | (finite ? 0 : AmdNative.FLAG_REF_NONFINITE) | AmdRuntime.FMA;
+        AmdNative.check(AmdNative.mraPlanesAoS(AmdRuntime.ctx(), d, a, rlo, rhi, AmdNative.waveletId(wavelet), boundary,
+                flags, flat));
+        for (int c = 0; c <= J; c++) {
+            out[c] = new double[n];
+            System.arraycopy(flat, c * n, out[c], 0, n);
+        }
+        return out;
+    }
+
+    /**
+     * {@code mra(decompose(signals[b], levels), finite)} for every signal, one engine call for the batch:
+     * {@code [B][levels + 1][N]}.  Validation as decomposeBatch, by the engine (FLAG_VALIDATE keeps the call on
+     * the masked inverses; {@code finite = true} trusts the caller instead).  Equal-length banks only.
+     */
+    public double[][][] mraBatch(double[][] signals, int levels, boolean finite) {
+        final int n = equalRows(signals);
+        final int batch = signals.length;
+        double[] flat = new double[Math.multiplyExact(Math.multiplyExact(levels + 1, batch), n)];
+        final int flags = AmdNative.FLAG_CORE_LEVELS | AmdNative.FLAG_FFT_SWITCH | AmdRuntime.FMA
+                | (finite ? 0 : AmdNative.FLAG_VALIDATE | AmdNative.FLAG_REF_NONFINITE);
+        AmdNative.check(AmdNative.mraAoS(AmdRuntime.ctx(), signals, wavelet.lowPassDecomposition(),
+                wavelet.highPassDecomposition(), AmdNative.waveletId(wavelet), boundary, levels, flags, flat));
+        double[][][] out = new double[batch][levels + 1][n];
+        for (int c = 0; c <= levels; c++) {
+            for (int b = 0; b < batch; b++) System.arraycopy(flat, (c * batch + b) * n, out[b][c], 0, n);
+        }
+        return out;
+    }
+
+    /** {@code mra(result, false)}: the reference's NaN / +-Inf spread kept. */
+    public double[][] mra(MultiLevelMODWTResult result) {
+        return mra(result, false);
+    }
+
     private double[] inverse(MultiLevelMODWTResult r, int mask, boolean approxZero) {
         final int J = r.getLevels();
         final int n = r.getSignalLength();

@@ -133,6 +133,13 @@ public final class AmdNative {
                                      int levels, int flags, double[] out);
     static native int energyPlanesAoS(long ctx, double[][][] details, double[][] approx, int flags, double[] out);
 
+    // multiresolution analysis of every signal (out: (levels + 1) * B * N doubles, [smooth, D1..DJ][B][N]): of the
+    // forward of the rows, and of coefficient planes the caller already has; lo / hi of one length
+    static native int mraAoS(long ctx, double[][] rows, double[] lo, double[] hi, int waveletId, int boundary,
+                             int levels, int flags, double[] out);
+    static native int mraPlanesAoS(long ctx, double[][][] details, double[][] approx, double[] lo, double[] hi,
+                                   int waveletId, int boundary, int flags, double[] out);
+
     // com.morphiqlabs.financial: FinancialAnalyzer's four metrics + the detail standard deviation of every price
     // row (out: 5 * B doubles, [5][B]); FinancialWaveletAnalyzer's Sharpe ratios of every return row (out: B)
     static native int finAnalyzeAoS(long ctx, double[][] prices, double[] lo, double[] hi, double anomalyK, int flags,

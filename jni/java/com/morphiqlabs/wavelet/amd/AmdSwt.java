@@ -205,6 +205,40 @@ public final class AmdSwt implements AutoCloseable {
         return reconstruct(r, mask, targetLevel != 0);
     }
 
+    /**
+     * {@code extractLevel(signal, levels, c)} for every c = 0 .. levels: {@code [levels + 1][N]}, row 0 the
+     * approximation's component, row j detail level j's -- the same bits from one forward and one engine call
+     * instead of levels + 1 of each.  Carries the inverse's flags (FLAG_REF_NONFINITE: the engine loops over the
+     * masked inverses); {@code finite = true} promises finite coefficients and lets the one-launch kernel run.
+     */
+    public double[][] extractAllLevels(double[] signal, int levels, boolean finite) {
+        MutableMultiLevelMODWTResult r = forward(signal, levels);
+        final int n = r.getSignalLength();
+        final double[] rlo = wavelet.lowPassReconstruction(), rhi = wavelet.highPassReconstruction();
+        double[][] out = new double[levels + 1][];
+        if (rlo.length != rhi.length) {  // a BiorthogonalWavelet: the masked two-length inverses, one by one
+            for (int c = 0; c <= levels; c++) out[c] = reconstruct(r, c == 0 ? 0 : 1 << (c - 1), c != 0);
+            return out;
+        }
+        double[][][] d = new double[levels][1][];
+        for (int l = 1; l <= levels; l++) d[l - 1][0] = r.getMutableDetailCoeffs(l);
+        double[][] a = {r.getMutableApproximationCoeffs()};
+        double[] flat = new double[Math.multiplyExact(levels + 1, n)];
+        final int guard = boundaryMode == BoundaryMode.PERIODIC ? 0 : AmdNative.FLAG_CORE_LEVELS;
+        AmdNative.check(AmdNative.mraPlanesAoS(AmdRuntime.ctx(), d, a, rlo, rhi, AmdNative.waveletId(wavelet), boundary,
+                guard | (finite ? 0 : AmdNative.FLAG_REF_NONFINITE) | AmdRuntime.FMA, flat));
+        for (int c = 0; c <= levels; c++) {
+            out[c] = new double[n];
+            System.arraycopy(flat, c * n, out[c], 0, n);
+        }
+        return out;
+    }
+
+    /** {@code extractAllLevels(signal, levels, false)}. */
+    public double[][] extractAllLevels(double[] signal, int levels) {
+        return extractAllLevels(signal, levels, false);
+    }
+
     /** cleanup() (:652-661): the engine context is the JVM's ({@link AmdRuntime}); nothing to release. */
     public void cleanup() {}
 

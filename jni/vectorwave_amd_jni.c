@@ -732,6 +732,87 @@ JNIEXPORT jint JNICALL VW_JNI(energyPlanesAoS)(JNIEnv *e, jclass c, jlong ctx, j
   return st;
 }
 
+/* ---- multiresolution analysis: out = (J+1) * B * N doubles, [smooth, D1..DJ][B][N] ----
+ * Row chunks like the energy natives: a chunk's [J+1][nb][N] result goes to rows b0 .. b0+nb of every component
+ * plane of the caller's flat [J+1][B][N] (which must fit a Java array: (J+1) * B * N <= Integer.MAX_VALUE). */
+static int mra_out_ok(JNIEnv *e, jdoubleArray out, jsize J, jsize B, jsize N) {
+  const size_t need = ((size_t)J + 1) * (size_t)B * (size_t)N;
+  if (need > (size_t)0x7fffffff) { arg_error(e, "(levels + 1) * batch * length exceeds a Java array"); return 0; }
+  return fin_out_ok(e, out, need);
+}
+
+static void mra_scatter(JNIEnv *e, jdoubleArray out, jsize J, jsize B, jsize N, jsize b0, jsize nb, const double *po) {
+  for (jsize k = 0; k <= J; ++k)  /* chunk plane k -> out[k][b0 .. b0+nb)[N] */
+    (*e)->SetDoubleArrayRegion(e, out, (jsize)(((size_t)k * B + b0) * N), (jsize)((size_t)nb * N),
+                               po + (size_t)k * nb * N);
+}
+
+/* signals double[B][N] -> out; vw_set_signal_base per chunk, so a validation error names the batch's signal */
+JNIEXPORT jint JNICALL VW_JNI(mraAoS)(JNIEnv *e, jclass c, jlong ctx, jobjectArray x, jdoubleArray lo, jdoubleArray hi,
+                                      jint wid, jint boundary, jint J, jint flags, jdoubleArray out) {
+  (void)c;
+  Taps tl, th;
+  if (!get_taps(e, lo, hi, &tl, &th)) return VW_ERR_ARG;
+  if (J < 1) return arg_error(e, "levels must be >= 1");
+  const jsize N = row_len(e, x);
+  if (N < 1) return VW_ERR_ARG;
+  const jsize B = (*e)->GetArrayLength(e, x);
+  if (!mra_out_ok(e, out, J, B, N)) return VW_ERR_ARG;
+  const jsize CB = chunk_rows(((size_t)J + 2) * (size_t)N, B);
+  int oom = 0;
+  double *px = out_buf(0, (size_t)CB * N, &oom), *po = out_buf(1, ((size_t)J + 1) * CB * N, &oom);
+  if (oom) return oom_error(e);
+  vw_status st = VW_OK;
+  for (jsize b0 = 0; b0 < B && st == VW_OK; b0 += CB) {
+    const jsize nb = B - b0 < CB ? B - b0 : CB;
+    if (!gather_rows(e, x, b0, nb, N, px)) { st = VW_ERR_ARG; break; }
+    vw_set_signal_base(b0);
+    st = vw_modwt_mra_f64(CTX(ctx), px, nb, N, N, tl.v, th.v, tl.n, wid, boundary, J, (unsigned)flags | HOST_FLAGS, po);
+    vw_set_signal_base(0);
+    if (st == VW_OK) mra_scatter(e, out, J, B, N, b0, nb, po);
+  }
+  trim_slots();
+  return st;
+}
+
+/* details double[J][B][N], approx double[B][N] -> out */
+JNIEXPORT jint JNICALL VW_JNI(mraPlanesAoS)(JNIEnv *e, jclass c, jlong ctx, jobjectArray details, jobjectArray approx,
+                                            jdoubleArray lo, jdoubleArray hi, jint wid, jint boundary, jint flags,
+                                            jdoubleArray out) {
+  (void)c;
+  Taps tl, th;
+  if (!get_taps(e, lo, hi, &tl, &th)) return VW_ERR_ARG;
+  if (!details) return null_error(e, "detailPerLevel cannot be null");
+  const jsize J = (*e)->GetArrayLength(e, details);
+  if (J < 1) return arg_error(e, "levels must be > 0");
+  const jsize N = row_len(e, approx);
+  if (N < 1) return VW_ERR_ARG;
+  const jsize B = (*e)->GetArrayLength(e, approx);
+  if (!planes_ok(e, details, J, B) || !mra_out_ok(e, out, J, B, N)) return VW_ERR_ARG;
+  const jsize CB = chunk_rows((2 * (size_t)J + 2) * (size_t)N, B);
+  int oom = 0;
+  double *pd = out_buf(0, (size_t)J * CB * N, &oom), *pa = out_buf(1, (size_t)CB * N, &oom);
+  double *po = out_buf(2, ((size_t)J + 1) * CB * N, &oom);
+  if (oom) return oom_error(e);
+  vw_status st = VW_OK;
+  for (jsize b0 = 0; b0 < B && st == VW_OK; b0 += CB) {
+    const jsize nb = B - b0 < CB ? B - b0 : CB;
+    for (jsize l = 0; l < J && st == VW_OK; ++l) {
+      jobjectArray pl = plane(e, details, l);
+      if (!gather_rows(e, pl, b0, nb, N, pd + (size_t)l * nb * N)) st = VW_ERR_ARG;
+      (*e)->DeleteLocalRef(e, pl);
+    }
+    if (st != VW_OK) break;
+    if (!gather_rows(e, approx, b0, nb, N, pa)) { st = VW_ERR_ARG; break; }
+    vw_set_signal_base(b0);
+    st = vw_mra_planes_f64(CTX(ctx), pd, pa, nb, N, tl.v, th.v, tl.n, wid, boundary, J, (unsigned)flags | HOST_FLAGS, po);
+    vw_set_signal_base(0);
+    if (st == VW_OK) mra_scatter(e, out, J, B, N, b0, nb, po);
+  }
+  trim_slots();
+  return st;
+}
+
 /* lo == NULL: vw_fin_sharpe_f64; else vw_fin_wavelet_sharpe_f64 */
 static jint fin_sharpe_rows(JNIEnv *e, jlong ctx, jobjectArray returns, const Taps *tl, const Taps *th, jint boundary,
                             jdouble riskFree, jint flags, jdoubleArray out) {

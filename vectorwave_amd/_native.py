@@ -83,6 +83,15 @@ SIGNATURES = {
     "vw_modwt_energy_f64": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int64, _dp, _dp, c_int, c_int, c_int,
                                     c_int, c_uint, c_void_p]),
     "vw_energy_planes_f64": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int, c_uint, c_void_p]),
+    # multiresolution analysis: out [J+1][B][N]
+    "vw_mra_planes_f64": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int64, _dp, _dp, c_int, c_int, c_int,
+                                  c_int, c_uint, c_void_p]),
+    "vw_mra_planes_f32": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int64, _dp, _dp, c_int, c_int, c_int,
+                                  c_int, c_uint, c_void_p]),
+    "vw_modwt_mra_f64": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int64, _dp, _dp, c_int, c_int, c_int,
+                                 c_int, c_uint, c_void_p]),
+    "vw_modwt_mra_f32": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int64, _dp, _dp, c_int, c_int, c_int,
+                                 c_int, c_uint, c_void_p]),
     "vw_fin_analyze_f64": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int64, _dp, _dp, c_int, c_double, c_uint,
                                    c_void_p]),
     "vw_fin_sharpe_f64": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int64, c_double, c_uint, c_void_p]),

@@ -1221,10 +1221,10 @@ static vw_status modwt_forward(vw_ctx* c, const T* x, int64_t B, int64_t N, int6
   return ok();
 }
 
-template <typename T>
-static vw_status modwt_inverse(vw_ctx* c, const T* details, const T* approx, int64_t B, int64_t N, const double* lo,
-                               const double* hi, int L, int wid, int boundary, int J, unsigned detail_mask,
-                               int approx_zero, unsigned flags, T* y, int Lhi = 0) {
+// The argument checks of vw_modwt_inverse_* (shared with the multiresolution calls, which make them too).
+static vw_status check_inverse(vw_ctx* c, const void* details, const void* approx, const void* y, const double* lo,
+                               const double* hi, int64_t B, int64_t N, int L, int boundary, int J, unsigned detail_mask,
+                               int approx_zero, unsigned flags) {
   if (!c) return fail(VW_ERR_NULL, "ctx is null");
   if (!y || !lo || !hi) return fail(VW_ERR_NULL, "null argument");
   if (!details && detail_mask) return fail(VW_ERR_NULL, "details is null");
@@ -1235,6 +1235,14 @@ static vw_status modwt_inverse(vw_ctx* c, const T* details, const T* approx, int
   // periodic inverse (VectorWaveSwtAdapter.reconstructPeriodic :444-474) wraps instead.
   if ((flags & VW_FLAG_CORE_LEVELS) && vw_upsampled_length(L, J) > N)
     return fail(VW_ERR_TOO_LARGE, "Upsampled reconstruction filter length exceeds signal length");
+  return VW_OK;
+}
+
+template <typename T>
+static vw_status modwt_inverse(vw_ctx* c, const T* details, const T* approx, int64_t B, int64_t N, const double* lo,
+                               const double* hi, int L, int wid, int boundary, int J, unsigned detail_mask,
+                               int approx_zero, unsigned flags, T* y, int Lhi = 0) {
+  VW_TRY(check_inverse(c, details, approx, y, lo, hi, B, N, L, boundary, J, detail_mask, approx_zero, flags));
   VW_TRY(check_bank(N, L, Lhi, J, flags, false));
   std::lock_guard<std::recursive_mutex> g(c->mu);
   hipSetDevice(c->device);
@@ -1877,6 +1885,144 @@ extern "C" vw_status vw_energy_planes_f64(vw_ctx* c, const double* details, cons
   VW_TRY(energy_planes_device(c, details, approx, B, N, J, flags, out));
   if (flags & VW_FLAG_SYNC) VW_HIP(hipStreamSynchronize(c->stream));
   return ok();
+}
+
+// ------------------------------------------------------------------------------------------------
+// Multiresolution analysis (vw_mra.hip): out[c] = the inverse with detail_mask = c ? 1 << (c-1) : 0 and
+// approx_zero = (c != 0) (VectorWaveSwtAdapter.extractLevel :576-598), every c in one call.
+// Timing families: "mra" (k_mra); the loop path's launches count as "inverse" / "inverse_level".
+
+// device pointers; k.y = out [J+1][B][N]; arguments checked by the caller
+template <typename T>
+static vw_status mra_planes_device(vw_ctx* c, InvCall<T> k) {
+  VW_TRY(capture_guard(c, k.flags));
+  k.cus = c->cus;
+  MraPlan<T> p;
+  plan_mra(c->tune, k, &p);
+  if (p.fused) {
+    MraArgs<T> a = p.args;
+    a.details = k.details; a.approx = k.approx; a.out = k.y;
+    copy_taps(a.lo, k.lo, k.L);
+    copy_taps(a.hi, k.hi, k.L);
+    LaunchTimer lt(c, "mra");
+    hipError_t e = launch_mra<T>(a, p.threads, p.lds, p.fma, p.nv, p.grid, c->stream);
+    if (e != hipSuccess) return fail(VW_ERR_DEVICE, "mra launch failed: %s", hipGetErrorString(e));
+  } else {
+    // the loop path: the J+1 masked inverses, each through its own plan
+    const size_t plane = (size_t)k.B * (size_t)k.N;
+    for (int comp = 0; comp <= k.J; ++comp) {
+      InvCall<T> ik = k;
+      ik.detail_mask = comp ? 1u << (comp - 1) : 0u;
+      ik.approx_zero = comp != 0;
+      ik.flags = k.flags & ~(unsigned)VW_FLAG_SYNC;
+      ik.y = k.y + (size_t)comp * plane;
+      VW_TRY(inverse_impl<T>(c, ik));
+    }
+  }
+  if (k.flags & VW_FLAG_SYNC) VW_HIP(hipStreamSynchronize(c->stream));
+  return VW_OK;
+}
+
+template <typename T>
+static vw_status mra_planes(vw_ctx* c, const T* details, const T* approx, int64_t B, int64_t N, const double* lo,
+                            const double* hi, int L, int wid, int boundary, int J, unsigned flags, T* out) {
+  VW_TRY(check_inverse(c, details, approx, out, lo, hi, B, N, L, boundary, J, ~0u, 0, flags));
+  if (flags & ~(unsigned)(VW_FLAG_CORE_LEVELS | VW_FLAG_FMA | VW_FLAG_HOST_MEMORY | VW_FLAG_SYNC | VW_FLAG_VALIDATE |
+                          VW_FLAG_REF_NONFINITE))
+    return fail(VW_ERR_ARG, "vw_mra_planes takes CORE_LEVELS, FMA, HOST_MEMORY, SYNC, VALIDATE and REF_NONFINITE only");
+  std::lock_guard<std::recursive_mutex> g(c->mu);
+  hipSetDevice(c->device);
+  InvCall<T> ik;
+  ik.details = details; ik.approx = approx; ik.B = B; ik.N = N; ik.lo = lo; ik.hi = hi; ik.L = L; ik.wid = wid;
+  ik.boundary = boundary; ik.J = J; ik.flags = flags; ik.y = out;
+  if (flags & VW_FLAG_HOST_MEMORY) {
+    if (c->capturing) return fail(VW_ERR_STATE, "host-memory calls cannot be captured (they synchronize)");
+    const size_t plane = (size_t)B * (size_t)N;
+    Staging s(c);
+    T *dd, *da, *dout;
+    VW_TRY(s.in(details, (size_t)J * plane, &dd));
+    VW_TRY(s.in(approx, plane, &da));
+    VW_TRY(s.in<T>(nullptr, ((size_t)J + 1) * plane, &dout));
+    ik.details = dd; ik.approx = da; ik.y = dout;
+    ik.flags = flags & ~(unsigned)(VW_FLAG_SYNC | VW_FLAG_HOST_MEMORY);
+    VW_TRY(mra_planes_device<T>(c, ik));
+    VW_TRY(s.out(out, dout, ((size_t)J + 1) * plane));
+    VW_HIP(hipStreamSynchronize(c->stream));
+    return ok();
+  }
+  VW_TRY(mra_planes_device<T>(c, ik));
+  return ok();
+}
+
+// device pointers; the forward's own plan and executor into the workspace (approx [B][N] | details [J][B][N]), then
+// the planes call on those coefficients
+template <typename T>
+static vw_status mra_device(vw_ctx* c, const T* x, int64_t B, int64_t N, int64_t ldx, const double* lo, const double* hi,
+                            int L, int wid, int boundary, int J, unsigned flags, T* out) {
+  VW_TRY(capture_guard(c, flags));
+  const size_t plane = (size_t)B * (size_t)N;
+  VW_TRY(ensure_ws2(c, ((size_t)J + 1) * plane * sizeof(T)));
+  T* app = reinterpret_cast<T*>(c->ws2);
+  T* det = app + plane;
+  FwdCall<T> fk;
+  fk.x = x; fk.B = B; fk.N = N; fk.ldx = ldx; fk.lo = lo; fk.hi = hi; fk.L = L; fk.boundary = boundary; fk.J = J;
+  fk.flags = flags & ~(unsigned)VW_FLAG_SYNC; fk.details = det; fk.approx = app;
+  VW_TRY(forward_impl<T>(c, fk));
+  InvCall<T> ik;
+  ik.details = det; ik.approx = app; ik.B = B; ik.N = N; ik.lo = lo; ik.hi = hi; ik.L = L; ik.wid = wid;
+  ik.boundary = boundary; ik.J = J; ik.flags = flags & ~(unsigned)VW_FLAG_FFT_SWITCH; ik.y = out;
+  return mra_planes_device<T>(c, ik);
+}
+
+template <typename T>
+static vw_status modwt_mra(vw_ctx* c, const T* x, int64_t B, int64_t N, int64_t ldx, const double* lo, const double* hi,
+                           int L, int wid, int boundary, int J, unsigned flags, T* out) {
+  // vw_modwt_forward_*'s checks, in its order, then the inverse's
+  VW_TRY(check_common(c, x, out, lo, hi, B, N, L, boundary));
+  if (ldx < N) return fail(VW_ERR_ARG, "ldx (%lld) < N (%lld)", (long long)ldx, (long long)N);
+  VW_TRY(check_levels(N, L, J, flags));
+  VW_TRY(check_inverse(c, x, x, out, lo, hi, B, N, L, boundary, J, ~0u, 0, flags));
+  if (flags & ~(unsigned)(VW_FLAG_CORE_LEVELS | VW_FLAG_FMA | VW_FLAG_HOST_MEMORY | VW_FLAG_SYNC | VW_FLAG_VALIDATE |
+                          VW_FLAG_REF_NONFINITE | VW_FLAG_FFT_SWITCH))
+    return fail(VW_ERR_ARG, "vw_modwt_mra takes CORE_LEVELS, FFT_SWITCH, FMA, HOST_MEMORY, SYNC, VALIDATE and REF_NONFINITE only");
+  std::lock_guard<std::recursive_mutex> g(c->mu);
+  hipSetDevice(c->device);
+  if (flags & VW_FLAG_HOST_MEMORY) {
+    if (c->capturing) return fail(VW_ERR_STATE, "host-memory calls cannot be captured (they synchronize)");
+    const size_t plane = (size_t)B * (size_t)N;
+    Staging s(c);
+    T *dx, *dout;
+    VW_TRY(s.in(x, (size_t)(B - 1) * ldx + N, &dx));  // (the last row's padding need not exist)
+    VW_TRY(s.in<T>(nullptr, ((size_t)J + 1) * plane, &dout));
+    VW_TRY(mra_device<T>(c, dx, B, N, ldx, lo, hi, L, wid, boundary, J,
+                         flags & ~(unsigned)(VW_FLAG_SYNC | VW_FLAG_HOST_MEMORY), dout));
+    VW_TRY(s.out(out, dout, ((size_t)J + 1) * plane));
+    VW_HIP(hipStreamSynchronize(c->stream));
+    return ok();
+  }
+  VW_TRY(mra_device<T>(c, x, B, N, ldx, lo, hi, L, wid, boundary, J, flags, out));
+  return ok();
+}
+
+extern "C" vw_status vw_mra_planes_f64(vw_ctx* c, const double* details, const double* approx, int64_t B, int64_t N,
+                                       const double* lo, const double* hi, int L, int wid, int boundary, int J,
+                                       unsigned flags, double* out) {
+  return mra_planes<double>(c, details, approx, B, N, lo, hi, L, wid, boundary, J, flags, out);
+}
+extern "C" vw_status vw_mra_planes_f32(vw_ctx* c, const float* details, const float* approx, int64_t B, int64_t N,
+                                       const double* lo, const double* hi, int L, int wid, int boundary, int J,
+                                       unsigned flags, float* out) {
+  return mra_planes<float>(c, details, approx, B, N, lo, hi, L, wid, boundary, J, flags, out);
+}
+extern "C" vw_status vw_modwt_mra_f64(vw_ctx* c, const double* x, int64_t B, int64_t N, int64_t ldx, const double* lo,
+                                      const double* hi, int L, int wid, int boundary, int J, unsigned flags,
+                                      double* out) {
+  return modwt_mra<double>(c, x, B, N, ldx, lo, hi, L, wid, boundary, J, flags, out);
+}
+extern "C" vw_status vw_modwt_mra_f32(vw_ctx* c, const float* x, int64_t B, int64_t N, int64_t ldx, const double* lo,
+                                      const double* hi, int L, int wid, int boundary, int J, unsigned flags,
+                                      float* out) {
+  return modwt_mra<float>(c, x, B, N, ldx, lo, hi, L, wid, boundary, J, flags, out);
 }
 
 // ------------------------------------------------------------------------------------------------

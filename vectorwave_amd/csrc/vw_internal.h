@@ -312,6 +312,31 @@ hipError_t launch_energy_fused(const EnergyArgs& a, int threads, int lds_bytes, 
 // tree = false: the reference's sequential sum per row (one lane per row); true: a workgroup tree per row
 hipError_t launch_energy_planes(const EnergyPlanesArgs& a, bool tree, int cus, hipStream_t st);
 
+// Multiresolution analysis (vw_mra.hip k_mra): out[0] = the smooth (a_J alone), out[c] = detail component c (d_c
+// alone), each the masked inverse with the branch passes over zeroed planes left out.
+constexpr int kMraUnrollMax = 14;  // longest filter with a tap-unrolled k_mra (vw_mra.hip launch_mra): from 16 taps on
+                                   // some instantiations spill to scratch
+template <typename T>
+struct MraArgs {
+  const T* details;     // [J][B][N]
+  const T* approx;      // [B][N]
+  T* out;               // [J+1][B][N]
+  long long B;
+  int N;
+  int J;
+  int hlpad;            // LDS offset of element 0 (multiple of the vector width)
+  int region1;          // element offset of the second region (the two are used ping-pong)
+  int vec_io;
+  int unrolled;
+  int level_ct;
+  int taps;
+  T lo[kMaxTaps];       // base taps * 1/sqrt(2)
+  T hi[kMaxTaps];
+  LevelDesc lv[kMaxLevels];  // inverse_levels' descriptors: dir_a / off_a / dir_d / off_d per branch
+};
+template <typename T>
+hipError_t launch_mra(const MraArgs<T>& a, int threads, int lds_bytes, bool fma, int nv, int grid, hipStream_t st);
+
 // Raise a kernel's dynamic-LDS limit past the 64 KiB default once per kernel instantiation AND
 // device (the attribute belongs to the device's copy of the function; a call per launch costs host
 // time).  `once` is a static of the caller, unique per kernel instantiation; several host threads

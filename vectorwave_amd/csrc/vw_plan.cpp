@@ -59,6 +59,7 @@ static const TuningKey kTuningTable[] = {
     VW_KEY("VW_REF_GRID", t.ref_grid = v < 0 ? d.ref_grid : v),
     VW_KEY("VW_LEVEL_CT", t.level_ct = v < 0 ? d.level_ct : v != 0),
     VW_KEY("VW_ENERGY_FUSED", t.energy_fused = v < 0 ? d.energy_fused : v),
+    VW_KEY("VW_MRA_FUSED", t.mra_fused = v < 0 ? d.mra_fused : v >= 2 ? 2 : v),
     VW_KEY("VW_BI", t.bi = v < 0 ? d.bi : v & 7),
     VW_KEY("VW_BI_LISTED", t.bi_listed = v < 0 ? d.bi_listed : v != 0),
     VW_KEY("VW_INV_WAVES", t.inv_waves = v == 6 || v == 8 ? v : d.inv_waves),
@@ -1081,6 +1082,59 @@ static void plan_inverse_taps(const Tuning& tu, const InvCall<T>& call, int taps
   if (!p->fused) plan_inverse_levels(tu, c, pair, p);
   reserve_ref<T>(tu, c.cus, c.B, c.N, p);
 }
+
+// ------------------------------------------------------------------------------------------------
+// Multiresolution analysis (vw_mra.hip, vw_plan.h).  The level descriptors are inverse_levels' for the call with
+// every plane kept, so each level's halos cover both branches' reach and the SYMMETRIC orientation and tau of
+// each branch are the inverse's own.  Two regions, always (the ping-pong is what makes a pass one barrier);
+// whole waves, as plan_energy.
+template <typename T>
+void plan_mra(const Tuning& tu, const InvCall<T>& c, MraPlan<T>* p) {
+  constexpr int V = vec_width<T>();
+  const int64_t N = c.N, nvec = (N + V - 1) / V;
+  const int L = c.L, J = c.J;
+  MraArgs<T>& a = p->args;
+  p->fma = c.flags & VW_FLAG_FMA;
+  p->fused = false;
+  if (tu.mra_fused == 0 || tu.force_tiled || c.single_level || J < 1 || J > kMaxLevels || L < 1 || L > kMaxTaps ||
+      (c.flags & (VW_FLAG_VALIDATE | VW_FLAG_REF_NONFINITE)) || (c.Lhi != 0 && c.Lhi != L) || c.thr)
+    return;
+  InvCall<T> k = c;
+  k.detail_mask = ~0u;
+  k.approx_zero = 0;
+  int max_hl = 0, max_hr = 0;
+  inverse_levels(k, L, L, a.lv, &max_hl, &max_hr);
+  const int64_t hlpad = round_up(max_hl, V);
+  const int64_t region = round_up(hlpad + nvec * V + max_hr + V, V);
+  int threads = 0, lds = 0, nv = 4;
+  bool fit = false;
+  if (!fused_plan(tu, N, V, sizeof(T), 2 * region, &threads, &nv, &lds, &fit)) return;
+  threads = (int)round_up(threads, 64);  // <= 512 (NV = 4) / 1024 (NV = 8): fused_plan's bounds are multiples of 64
+  fit = (int64_t)(nv - 1) * threads <= nvec;
+  const bool io_aligned = (N % V == 0) && aligned16(c.details) && aligned16(c.approx) && aligned16(c.y);
+  a.B = c.B; a.N = (int)N; a.J = J;
+  a.taps = L;
+  for (int j = 0; j < J; ++j) set_halo_images(a.lv[j], N, 0, V, threads, nv);
+  a.hlpad = (int)hlpad;
+  a.region1 = (int)region;
+  a.vec_io = io_aligned;
+  a.unrolled = io_aligned && fit && L <= tu.unroll_max && L <= kMraUnrollMax && has_unrolled_taps(L);
+  a.level_ct = tu.level_ct;
+  // "On only where no slower" (DESIGN.md 8j): where the masked inverses run their tap-unrolled kernels and k_mra
+  // has only its runtime-L body -- listed lengths past kMraUnrollMax on aligned full-slab rows -- the loop wins
+  // (coif5 fp32 16384 x 8192, J = 6: 14.3 ms against 22.9 ms); VW_MRA_FUSED=2 fuses there too.
+  if (tu.mra_fused == 1 && !a.unrolled && io_aligned && fit && L <= tu.unroll_max && has_unrolled_taps(L)) return;
+  // a few workgroups per CU, grid-stride over the rows: what LDS and the kernel's wave bounds (k_mra: 6 waves per
+  // SIMD at NV = 4 unless a long filter's unrolled body runs, else 4) let be resident at once
+  const int wpe = (nv <= 4 && !(a.unrolled && L > 8)) ? 6 : 4;
+  const int by_waves = std::max(1, wpe * 4 / (threads / 64));
+  const int by_lds = std::max(1, kLdsBytes / std::max(lds, 1));
+  p->grid = (int)std::min<int64_t>(c.B, (int64_t)std::max(c.cus, 1) * std::min(by_waves, by_lds));
+  p->threads = threads; p->nv = nv; p->lds = lds;
+  p->fused = true;
+}
+template void plan_mra<float>(const Tuning&, const InvCall<float>&, MraPlan<float>*);
+template void plan_mra<double>(const Tuning&, const InvCall<double>&, MraPlan<double>*);
 
 template <typename T>
 void plan_forward(const Tuning& tu, const FwdCall<T>& c, FwdPlan<T>* p) {

@@ -71,6 +71,8 @@ struct Tuning {
   int inv_waves = 6;           // VW_INV_WAVES=6|8: waves per SIMD k_inverse_seq's PLAIN form is compiled for -- 8 (64 VGPRs)
                                // lets four 512-thread workgroups share a CU where 6 lets three; measured no
                                // faster than 6 on the db4 step (profiles/r09/ab_db4_inv_waves.log)
+  int mra_fused = 1;           // VW_MRA_FUSED=0: vw_mra_planes_* / vw_modwt_mra_* never run k_mra (J+1 masked inverses instead);
+                               // 2: k_mra wherever it fits, also where it measured slower than the loop (plan_mra)
   int bi_listed = 1;           // VW_BI_LISTED=0: a two-length bank runs max(Llo, Lhi) taps even where that count is not in
                                // VW_TAP_LIST (the runtime-L kernels); 1: one more zero tap where that reaches a listed count
 };
@@ -192,6 +194,22 @@ struct EnergyPlan {
   EnergyArgs args{};     // every non-pointer field
 };
 void plan_energy(const Tuning& tu, const FwdCall<double>& c, EnergyPlan* p);
+
+// vw_mra_planes_* / vw_modwt_mra_* (vw_mra.hip): whether k_mra runs and with what launch shape.  `c` is the inverse's
+// call with y = out [J+1][B][N]; its detail_mask / approx_zero are not read.  Fused where two LDS regions (the row
+// plus the longest level's halos for both branches) fit with fused_plan's thread and NV choice; never for
+// single_level, VW_FORCE_TILED, VW_FLAG_VALIDATE / VW_FLAG_REF_NONFINITE (k_mra skips the zeroed planes, which
+// only finite data allows), a two-length bank or VW_MRA_FUSED=0.  Not fused: the LOOP PATH -- the executor issues
+// J+1 masked inverses (plan_inverse each), component c into out[c]: the same bits on any shape the inverse takes.
+template <typename T>
+struct MraPlan {
+  bool fused = false;
+  bool fma = false;
+  int threads = 0, nv = 4, lds = 0;
+  int grid = 0;          // workgroups (grid-stride over the rows)
+  MraArgs<T> args{};     // every non-pointer field
+};
+template <typename T> void plan_mra(const Tuning& tu, const InvCall<T>& c, MraPlan<T>* p);
 
 // Banks with two lengths (Lhi != 0 and != L; the _bi_ entry points) run the same kernels on the PADDED ROUTE: the
 // shorter filter is zero-extended to args.taps = max(L, Lhi), or one tap further where only that count has

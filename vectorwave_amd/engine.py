@@ -352,6 +352,37 @@ class Engine:
                                              self._ptr(out, dev)))
         return out
 
+    # -- multiresolution analysis (vw_mra_planes_* / vw_modwt_mra_*) -------------------------------
+    def mra_planes(self, details, approx, lo: Sequence[float], hi: Sequence[float], wavelet_id: int, boundary: int,
+                   flags: int = 0):
+        """Every additive component of the coefficient planes details [J,B,N] (or [J,N]) and approx [B,N] (or [N])
+        -> [J+1,(B,)N]: row 0 the smooth (approximation alone), row j detail component j (d_j alone) -- each the
+        inverse with every other plane zeroed, bit for bit without FLAG_FMA.  One launch where the rows fit and the
+        flags promise finite data (neither FLAG_VALIDATE nor FLAG_REF_NONFINITE), else the J+1 masked inverses."""
+        aa, dev, ap, f32 = self._prep(approx)
+        da, ddev, dp, _ = self._prep(details, np.float32 if f32 else np.float64)
+        if ddev != dev or da.ndim != aa.ndim + 1 or tuple(da.shape[1:]) != tuple(aa.shape) or da.shape[0] < 1:
+            raise ValueError("details must be [J] + approx.shape with J >= 1, in the same memory as approx")
+        J = int(da.shape[0])
+        B, N = (1, aa.shape[0]) if aa.ndim == 1 else aa.shape
+        out = self._empty(aa, dev, (J + 1,) + tuple(aa.shape))
+        fn = self.lib.vw_mra_planes_f32 if f32 else self.lib.vw_mra_planes_f64
+        _check(fn(self.ctx, dp, ap, B, N, nat.taps_array(lo), nat.taps_array(hi), _one_length(lo, hi, "mra_planes"),
+                  wavelet_id, boundary, J, self._flags(flags, dev), self._ptr(out, dev)))
+        return out
+
+    def mra(self, x, lo: Sequence[float], hi: Sequence[float], wavelet_id: int, boundary: int, levels: int,
+            flags: int = 0):
+        """Multi-level forward of x [N] or [B,N], then mra_planes on its coefficients -> [J+1,(B,)N].  The
+        coefficients stay in the context workspace; FLAG_FFT_SWITCH applies to the forward only."""
+        xa, dev, xp, f32 = self._prep(x)
+        B, N = (1, xa.shape[0]) if xa.ndim == 1 else xa.shape
+        out = self._empty(xa, dev, (levels + 1,) + tuple(xa.shape))
+        fn = self.lib.vw_modwt_mra_f32 if f32 else self.lib.vw_modwt_mra_f64
+        _check(fn(self.ctx, xp, B, N, N, nat.taps_array(lo), nat.taps_array(hi), _one_length(lo, hi, "mra"),
+                  wavelet_id, boundary, levels, self._flags(flags, dev), self._ptr(out, dev)))
+        return out
+
     def transpose(self, a, rows: int, cols: int):
         """out[c][r] = a[r][c] (a: rows*cols elements, any shape) -> flat [cols*rows] array."""
         aa, dev, ap, f32 = self._prep(a)

@@ -17,7 +17,7 @@ import numpy as np
 from . import _native as nat
 from .engine import Engine, _is_device_tensor, max_levels as _max_levels
 from .errors import ErrorCode, InvalidArgumentException, InvalidSignalException
-from .wavelets import Wavelet, require_orthogonal
+from .wavelets import Wavelet, is_biorthogonal, require_orthogonal
 
 try:
     import torch
@@ -41,6 +41,11 @@ def _check_boundary(mode: BoundaryMode) -> None:
 
 def _copy(a):
     return a.clone() if _is_device_tensor(a) else np.array(a, copy=True)
+
+
+def _stack(parts):
+    """Arrays of one shape and memory kind along a new leading axis (a copy, no arithmetic)."""
+    return torch.stack(list(parts)) if _is_device_tensor(parts[0]) else np.stack([np.asarray(p) for p in parts])
 
 
 def _energy(a) -> float:
@@ -394,6 +399,44 @@ class MultiLevelMODWTTransform:
             self._fma | nat.FLAG_REF_NONFINITE | (nat.FLAG_CORE_LEVELS if guard else 0), detail_mask=mask,
             approx_zero=approx_zero,
             shape=tuple(result.approximation_array.shape))
+
+    def mra(self, result: MultiLevelMODWTResult, finite: bool = False, guard: bool = True):
+        """Multiresolution analysis of a decomposition: [J+1, (B,) N] with row 0 the smooth (the approximation alone,
+        every detail zeroed) and row j detail component j (only d_j kept) -- the rows add up to the signal, and
+        each is what ``reconstructLevels`` / ``VectorWaveSwtAdapter.extractLevel`` give for that one level, bit
+        for bit (getRelativeEnergyDistribution's [approx, d1..dJ] order).  One engine call instead of J+1.
+
+        ``finite=True`` promises finite coefficients: the call then drops FLAG_REF_NONFINITE and may run the
+        one-launch kernel, which skips the zeroed planes (0 * Inf would be NaN in the reference's full sums).
+        By default the reference's NaN / Inf spread is kept and the engine loops over the masked inverses.
+        A biorthogonal wavelet loops over the two-length inverse calls."""
+        if result is None:
+            raise TypeError("result cannot be null")
+        w = self.wavelet
+        J = result.getLevels()
+        if is_biorthogonal(w):
+            parts = [self._reconstruct(result, (1 << (c - 1)) if c else 0, c != 0, guard=guard) for c in range(J + 1)]
+            return _stack(parts)
+        flags = self._fma | (0 if finite else nat.FLAG_REF_NONFINITE) | (nat.FLAG_CORE_LEVELS if guard else 0)
+        return _engine_for(result.approximation_array).mra_planes(
+            result.details_array, result.approximation_array, w.lowPassReconstruction(), w.highPassReconstruction(),
+            w.wavelet_id, int(self.boundaryMode), flags)
+
+    def mraBatch(self, signals, levels: Optional[int] = None, finite: bool = False):
+        """``mra(decompose(signals, levels))`` for signals [B, N] (or [N]): [J+1, (B,) N], in one engine call that
+        keeps the coefficients in its workspace.  Validation as decompose (non-finite input and the level cap are
+        refused); ``finite=True`` promises finite signals instead: no validation pass, and the one-launch kernel
+        may run."""
+        w = self.wavelet
+        if is_biorthogonal(w):
+            return self.mra(self.decompose(signals, levels), finite=finite)
+        _validate_signal(signals)
+        if levels is None:
+            levels = self.getMaximumLevels(_length(signals))
+        flags = (nat.FLAG_CORE_LEVELS | nat.FLAG_FFT_SWITCH | self._fma |
+                 (0 if finite else nat.FLAG_VALIDATE | nat.FLAG_REF_NONFINITE))
+        return _engine_for(signals).mra(signals, w.lowPassDecomposition(), w.highPassDecomposition(), w.wavelet_id,
+                                        int(self.boundaryMode), levels, flags)
 
     def reconstruct(self, result: MultiLevelMODWTResult):
         """reconstruct :339-349 (cascade J..1; K4 periodic / K5 zero / K6 symmetric)."""

@@ -127,3 +127,11 @@ class VectorWaveSwtAdapter:
             mask = 0
         return self.modwtTransform._reconstruct(res, mask, targetLevel != 0,
                                                 guard=self.boundaryMode != BoundaryMode.PERIODIC)
+
+    def extractAllLevels(self, signal, levels: int, finite: bool = False):
+        """``extractLevel(signal, levels, c)`` for every c = 0 .. levels, stacked: [levels+1, (B,) N], row 0 the
+        approximation's component, row j detail level j's -- the same bits, from one forward and one engine call
+        instead of levels+1 of each.  ``finite=True`` promises finite coefficients and lets the one-launch kernel
+        run (see MultiLevelMODWTTransform.mra)."""
+        res = self.forward(signal, levels)
+        return self.modwtTransform.mra(res, finite=finite, guard=self.boundaryMode != BoundaryMode.PERIODIC)
