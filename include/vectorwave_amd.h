@@ -505,6 +505,27 @@ VW_API vw_status vw_capture_end(vw_ctx *ctx, vw_graph **out);
  * launches of the last replay of the call. */
 VW_API vw_status vw_graph_launch(vw_graph *graph, int64_t count);
 VW_API vw_status vw_graph_destroy(vw_graph *graph);
+/* What a capture recorded: the graph's kernel nodes, and how many forward -> inverse pairs became one
+ * round-trip launch (below; each counts one kernel node).  Either pointer may be NULL. */
+VW_API vw_status vw_graph_stats(vw_graph *graph, int *kernel_nodes, int *fused_pairs);
+
+/* ---- forward + inverse of the same rows in one launch --------------------------------------------
+ * vw_modwt_forward_f64(x -> details, approx) followed by vw_modwt_inverse_f64(details, approx -> y, every level
+ * kept): the same arrays, bit for bit, in both accumulation modes.  Where the pair is eligible -- device memory,
+ * fp64, PERIODIC, a filter of at most 8 taps, rows the persistent forward takes whole (N a multiple of 512
+ * samples up to 4096), no VALIDATE / REF_NONFINITE, y apart from x / details / approx -- one kernel runs both
+ * halves per row, keeps a_J and d_J in registers and reads the other detail rows back right after storing them;
+ * otherwise the two kernels run.  lo / hi: the
+ * analysis pair, rlo / rhi: the synthesis pair, L taps each.
+ * While a context is capturing (vw_capture_begin), a vw_modwt_forward_f64 directly followed by its
+ * vw_modwt_inverse_f64 is recorded as this one launch too (switch VW_PAIR_FUSE, 0 = off; never with timing
+ * enabled: the per-kernel event nodes keep the two kernels). */
+VW_API vw_status vw_modwt_roundtrip_f64(vw_ctx *ctx, const double *x, int64_t B, int64_t N, int64_t ldx,
+                                        const double *lo, const double *hi, const double *rlo, const double *rhi,
+                                        int L, int wavelet_id, int boundary, int J, unsigned flags, double *details,
+                                        double *approx, double *y);
+/* Resident workgroups per compute unit of that launch for rows of N samples (0: the shape is not eligible). */
+VW_API vw_status vw_roundtrip_occupancy(vw_ctx *ctx, int64_t N, int L, int J, unsigned flags, int *per_cu);
 
 /* ---- pipelined round trips ---------------------------------------------------
  * A caller that runs forward + inverse over successive batches (a server's per-batch loop over

@@ -128,6 +128,11 @@ SIGNATURES = {
     "vw_capture_end": (c_int, [c_void_p, POINTER(c_void_p)]),
     "vw_graph_launch": (c_int, [c_void_p, c_int64]),
     "vw_graph_destroy": (c_int, [c_void_p]),
+    "vw_graph_stats": (c_int, [c_void_p, POINTER(c_int), POINTER(c_int)]),
+    # forward + inverse in one launch: (lo, hi) analysis, (rlo, rhi) synthesis
+    "vw_modwt_roundtrip_f64": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int64, _dp, _dp, _dp, _dp, c_int, c_int,
+                                       c_int, c_int, c_uint, c_void_p, c_void_p, c_void_p]),
+    "vw_roundtrip_occupancy": (c_int, [c_void_p, c_int64, c_int, c_int, c_uint, POINTER(c_int)]),
     # pipelined round trips: per-set arrays of device pointers (c_void_p * sets)
     "vw_pipeline_create": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int64,
                                    c_int64, _dp, _dp, c_int, c_int, c_int, c_int, c_uint, POINTER(c_void_p)]),

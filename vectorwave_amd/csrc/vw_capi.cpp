@@ -68,6 +68,17 @@ struct vw_graph;
 struct vw_ctx;
 static void kill_pipelines_of(vw_ctx* c);
 
+// A forward recorded during the current capture that the NEXT call may turn into a round trip (try_pair_fuse):
+// its kernel node, and the call as it was launched.  No pointer of the caller's that may die is kept: the taps
+// are in `args`.
+struct PairPending {
+  bool valid = false;
+  hipGraphNode_t node = nullptr;
+  FwdCall<double> call;
+  FwdPlan<double> plan;
+  FwdArgs<double> args;
+};
+
 struct vw_ctx {
   int device = 0;
   hipStream_t stream = nullptr;
@@ -93,6 +104,8 @@ struct vw_ctx {
   size_t med_bytes = 0;
   int* nf = nullptr;           // VW_FLAG_REF_NONFINITE row flags [nf_rows], zero between calls (vw_ref.hip)
   int64_t nf_rows = 0;
+  PairPending pair;            // VW_PAIR_FUSE: the forward the next call may fuse with (capture only)
+  int fused_pairs = 0;         // round trips recorded by the current capture
 };
 
 struct vw_graph {
@@ -102,6 +115,7 @@ struct vw_graph {
   std::vector<TimedLaunch> timed;  // event-record nodes (timing enabled at capture)
   hipGraph_t graph = nullptr;
   hipGraphExec_t exec = nullptr;
+  int fused_pairs = 0;             // forward -> inverse pairs recorded as one k_roundtrip node
 };
 
 // Frees the HIP objects of a graph (its context's device must be current).
@@ -169,6 +183,7 @@ struct LaunchTimer {
   TimedLaunch tl;
   bool on;
   LaunchTimer(vw_ctx* ctx, const char* family) : c(ctx), on(ctx->timing) {
+    c->pair.valid = false;  // whatever launches next, the remembered forward is no longer the previous call
     if (!on) return;
     tl.family = family;
     if (c->capturing) {
@@ -386,6 +401,8 @@ extern "C" vw_status vw_capture_begin(vw_ctx* c) {
   VW_HIP(hipStreamBeginCapture(c->stream, hipStreamCaptureModeThreadLocal));
   c->capturing = true;
   c->captured.clear();
+  c->pair.valid = false;
+  c->fused_pairs = 0;
   return ok();
 }
 
@@ -395,6 +412,7 @@ extern "C" vw_status vw_capture_end(vw_ctx* c, vw_graph** out) {
   if (!c->capturing) return fail(VW_ERR_STATE, "not capturing");
   hipSetDevice(c->device);
   c->capturing = false;
+  c->pair.valid = false;
   std::vector<TimedLaunch> timed;
   timed.swap(c->captured);
   auto drop = [&] { for (auto& t : timed) { hipEventDestroy(t.start); hipEventDestroy(t.stop); } };
@@ -418,6 +436,7 @@ extern "C" vw_status vw_capture_end(vw_ctx* c, vw_graph** out) {
   gr->ws_gen = c->ws_gen;
   gr->graph = graph;
   gr->exec = exec;
+  gr->fused_pairs = c->fused_pairs;
   c->graphs.insert(gr);
   *out = gr;
   return ok();
@@ -443,6 +462,29 @@ extern "C" vw_status vw_graph_launch(vw_graph* gr, int64_t count) {
                      c->pending.end());
     for (const auto& t : gr->timed) c->pending.push_back(t);
   }
+  return ok();
+}
+
+extern "C" vw_status vw_graph_stats(vw_graph* gr, int* kernel_nodes, int* fused_pairs) {
+  if (!gr) return fail(VW_ERR_NULL, "graph is null");
+  vw_ctx* c = gr->ctx;
+  if (!c) return fail(VW_ERR_STATE, "the context of this graph was destroyed");
+  std::lock_guard<std::recursive_mutex> g(c->mu);
+  hipSetDevice(c->device);
+  if (kernel_nodes) {
+    size_t n = 0;
+    VW_HIP(hipGraphGetNodes(gr->graph, nullptr, &n));
+    std::vector<hipGraphNode_t> nodes(n);
+    if (n) VW_HIP(hipGraphGetNodes(gr->graph, nodes.data(), &n));
+    int kernels = 0;
+    for (size_t i = 0; i < n; ++i) {
+      hipGraphNodeType ty;
+      VW_HIP(hipGraphNodeGetType(nodes[i], &ty));
+      if (ty == hipGraphNodeTypeKernel) ++kernels;
+    }
+    *kernel_nodes = kernels;
+  }
+  if (fused_pairs) *fused_pairs = gr->fused_pairs;
   return ok();
 }
 
@@ -915,6 +957,105 @@ static vw_status forward_steps(vw_ctx* c, const FwdCall<T>& k, const FwdPlan<T>&
   return VW_OK;
 }
 
+// ------------------------------------------------------------------------------------------------
+// Forward -> inverse pairs as one k_roundtrip launch (vw_pair.hip; vw_plan.h pair_fusable; VW_PAIR_FUSE).
+// While capturing with timing off, an eligible forward is launched as ever and its kernel node remembered; if
+// the very next call is the inverse of its coefficients, that node's parameters are replaced by the round trip's
+// and no inverse node is added.  Nothing is held back: work a caller captures on the stream between the two calls
+// keeps its place, and ends the pairing (the stream's capture dependencies are then no longer that node alone).
+
+// The one node the next operation captured on `st` would depend on (false: not capturing, or not exactly one).
+static bool capture_tail(hipStream_t st, hipGraphNode_t* node) {
+  hipStreamCaptureStatus status;
+  unsigned long long id = 0;
+  hipGraph_t g = nullptr;
+  const hipGraphNode_t* deps = nullptr;
+  size_t ndeps = 0;
+  if (hipStreamGetCaptureInfo_v2(st, &status, &id, &g, &deps, &ndeps) != hipSuccess) {
+    (void)hipGetLastError();
+    return false;
+  }
+  if (status != hipStreamCaptureStatusActive || ndeps != 1 || !deps) return false;
+  *node = deps[0];
+  return true;
+}
+
+// what a forward plan must be for its launch to become a round trip (pair_fusable decides on the pair)
+static bool pair_forward_shape(const FwdPlan<double>& p) {
+  return p.fused && p.kernel == kFwdPersist && p.args.level_ct && p.nv == 4 && p.args.taps <= kPairMaxTaps;
+}
+
+// After an eligible forward's launch.  Uncaptured: the round trip's LDS limit and occupancy, which a capture
+// cannot query.  Captured: remember the node.
+static void pair_after_forward(vw_ctx* c, const FwdCall<double>& k, const FwdPlan<double>& p, const FwdArgs<double>& a) {
+  c->pair.valid = false;
+  if (!c->tune.pair_fuse || !pair_forward_shape(p)) return;
+  if (!c->capturing) {
+    if (pair_prepare(a.taps, p.fma, p.threads, p.lds, nullptr) != hipSuccess) (void)hipGetLastError();
+    return;
+  }
+  if (c->timing || p.ref_nf || p.validate) return;
+  hipGraphNode_t node = nullptr;
+  hipGraphNodeType ty;
+  if (!capture_tail(c->stream, &node)) return;
+  if (hipGraphNodeGetType(node, &ty) != hipSuccess || ty != hipGraphNodeTypeKernel) {
+    (void)hipGetLastError();
+    return;
+  }
+  c->pair.node = node;
+  c->pair.call = k;
+  c->pair.call.lo = c->pair.call.hi = nullptr;  // the caller's arrays: a.lo / a.hi hold their values
+  c->pair.plan = p;
+  c->pair.args = a;
+  c->pair.valid = true;
+}
+static void pair_after_forward(vw_ctx* c, const FwdCall<float>&, const FwdPlan<float>&, const FwdArgs<float>&) {
+  c->pair.valid = false;
+}
+
+// The round trip's arguments: the forward's as launched, the inverse's taps, output and right halos.
+static void pair_args(const FwdArgs<double>& f, const InvCall<double>& k, const InvPlan<double>& p, PairArgs<double>* a) {
+  a->f = f;
+  a->y = k.y;
+  double lo[kMaxTaps], hi[kMaxTaps];
+  copy_bank(lo, hi, k, p.args.taps, p.args.taps_hi);
+  for (int i = 0; i < kPairMaxTaps; ++i) { a->ilo[i] = lo[i]; a->ihi[i] = hi[i]; }
+  for (int j = 0; j < kMaxLevels; ++j) { a->hr[j] = p.args.lv[j].hr; a->own[j] = p.args.lv[j].own; }
+}
+
+// At an inverse call: true when the remembered forward's node now runs the round trip (no inverse launch needed).
+static bool try_pair_fuse(vw_ctx* c, const InvCall<double>& k, const InvPlan<double>& p) {
+  const bool pending = c->pair.valid;
+  c->pair.valid = false;
+  if (!pending || !c->capturing || c->timing || !c->tune.pair_fuse) return false;
+  hipGraphNode_t tail = nullptr;
+  if (!capture_tail(c->stream, &tail) || tail != c->pair.node) return false;  // something was captured in between
+  if (!pair_fusable(c->pair.call, c->pair.plan, k, p)) return false;
+  const FwdPlan<double>& fp = c->pair.plan;
+  PairLaunch l;
+  if (!pair_launch_shape(fp.args.taps, fp.fma, fp.threads, fp.lds, k.B, c->cus, &l)) return false;  // never run uncaptured
+  PairArgs<double> a;
+  pair_args(c->pair.args, k, p, &a);
+  void* params[] = {&a};
+  hipKernelNodeParams np;
+  memset(&np, 0, sizeof(np));
+  np.func = const_cast<void*>(l.func);
+  np.gridDim = dim3(l.grid);
+  np.blockDim = dim3(l.threads);
+  np.sharedMemBytes = l.lds;
+  np.kernelParams = params;
+  if (hipGraphKernelNodeSetParams(c->pair.node, &np) != hipSuccess) {
+    (void)hipGetLastError();  // this runtime keeps the node as it is: the inverse is launched as ever
+    return false;
+  }
+  ++c->fused_pairs;
+  return true;
+}
+static bool try_pair_fuse(vw_ctx* c, const InvCall<float>&, const InvPlan<float>&) {
+  c->pair.valid = false;
+  return false;
+}
+
 // Forward (multi-level and single-level share this path).
 template <typename T>
 static vw_status forward_impl(vw_ctx* c, FwdCall<T> k) {
@@ -938,12 +1079,15 @@ static vw_status forward_impl(vw_ctx* c, FwdCall<T> k) {
     a.nf_flag = p.nf_probed ? c->nf : nullptr;
     for (int j = 0; j < k.J; ++j) a.hist[j] = k.hist ? k.hist[j] : nullptr;
     copy_bank(a.lo, a.hi, k, a.taps, a.taps_hi);
-    LaunchTimer lt(c, "forward");
-    hipError_t e = p.kernel == kFwdMfma    ? mfma_forward(a, p.lds, c->stream)
-                 : p.kernel == kFwdBlk     ? launch_forward_blk<T>(a, p.threads, p.lds, p.fma, p.nv, c->stream)
-                 : p.kernel == kFwdPersist ? launch_forward_persist<T>(a, p.threads, p.lds, p.fma, p.nv, c->stream)
-                                           : launch_forward_fused<T>(a, p.threads, p.lds, p.fma, p.nv, c->stream);
-    if (e != hipSuccess) return fail(VW_ERR_DEVICE, "forward launch failed: %s", hipGetErrorString(e));
+    {
+      LaunchTimer lt(c, "forward");
+      hipError_t e = p.kernel == kFwdMfma    ? mfma_forward(a, p.lds, c->stream)
+                   : p.kernel == kFwdBlk     ? launch_forward_blk<T>(a, p.threads, p.lds, p.fma, p.nv, c->stream)
+                   : p.kernel == kFwdPersist ? launch_forward_persist<T>(a, p.threads, p.lds, p.fma, p.nv, c->stream)
+                                             : launch_forward_fused<T>(a, p.threads, p.lds, p.fma, p.nv, c->stream);
+      if (e != hipSuccess) return fail(VW_ERR_DEVICE, "forward launch failed: %s", hipGetErrorString(e));
+    }
+    pair_after_forward(c, k, p, a);  // VW_PAIR_FUSE: the next call may be this forward's inverse
   } else {
     VW_TRY(forward_steps(c, k, p));
   }
@@ -1041,6 +1185,7 @@ static vw_status inverse_impl(vw_ctx* c, InvCall<T> k) {
   plan_inverse(c->tune, k, &p);
   if (p.error != VW_OK) return fail((vw_status)p.error, "%s", p.msg);
   VW_TRY(reserve(c, p.res));
+  if (try_pair_fuse(c, k, p)) return VW_OK;  // the captured forward before this call now runs both (VW_PAIR_FUSE)
   if (p.fused) {
     InvArgs<T> a = p.args;
     a.details = k.details; a.approx = k.approx; a.y = k.y; a.thr = k.thr;
@@ -1280,6 +1425,77 @@ extern "C" vw_status vw_modwt_inverse_f32(vw_ctx* c, const float* details, const
                                           int J, unsigned detail_mask, int approx_zero, unsigned flags, float* y) {
   return modwt_inverse<float>(c, details, approx, B, N, lo, hi, L, wid, boundary, J, detail_mask, approx_zero, flags,
                               y);
+}
+
+// Forward, then inverse of its coefficients (include/vectorwave_amd.h): one k_roundtrip launch where the pair is
+// eligible (pair_fusable) and the launch shape is, or can be made, ready; the two calls otherwise.
+extern "C" vw_status vw_modwt_roundtrip_f64(vw_ctx* c, const double* x, int64_t B, int64_t N, int64_t ldx,
+                                            const double* lo, const double* hi, const double* rlo, const double* rhi,
+                                            int L, int wid, int boundary, int J, unsigned flags, double* details,
+                                            double* approx, double* y) {
+  if (c && x && details && approx && y && lo && hi && rlo && rhi && !(flags & VW_FLAG_HOST_MEMORY) && B > 0 && N > 0 &&
+      ldx >= N && L >= 1 && L <= kPairMaxTaps && J >= 1 && J <= kMaxLevels && boundary == VW_PERIODIC) {
+    std::lock_guard<std::recursive_mutex> g(c->mu);
+    hipSetDevice(c->device);
+    FwdCall<double> fk;
+    fk.x = x; fk.B = B; fk.N = N; fk.ldx = ldx; fk.lo = lo; fk.hi = hi; fk.L = L; fk.boundary = boundary; fk.J = J;
+    fk.flags = flags; fk.details = details; fk.approx = approx; fk.cus = c->cus;
+    InvCall<double> ik;
+    ik.details = details; ik.approx = approx; ik.B = B; ik.N = N; ik.lo = rlo; ik.hi = rhi; ik.L = L; ik.wid = wid;
+    ik.boundary = boundary; ik.J = J; ik.flags = flags; ik.y = y; ik.cus = c->cus;
+    FwdPlan<double> fp;
+    InvPlan<double> ip;
+    if (c->tune.pair_fuse && check_levels(N, L, J, flags) == VW_OK && capture_guard(c, flags) == VW_OK) {
+      plan_forward(c->tune, fk, &fp);
+      plan_inverse(c->tune, ik, &ip);
+      PairLaunch l;
+      if (pair_fusable(fk, fp, ik, ip) &&
+          (c->capturing || pair_prepare(fp.args.taps, fp.fma, fp.threads, fp.lds, nullptr) == hipSuccess) &&
+          pair_launch_shape(fp.args.taps, fp.fma, fp.threads, fp.lds, B, c->cus, &l)) {
+        FwdArgs<double> f = fp.args;
+        f.x = x; f.details = details; f.approx = approx;
+        f.bad = c->bad;
+        copy_bank(f.lo, f.hi, fk, f.taps, f.taps_hi);
+        PairArgs<double> a;
+        pair_args(f, ik, ip, &a);
+        {
+          LaunchTimer lt(c, "roundtrip");
+          hipError_t e = launch_roundtrip(a, l, c->stream);
+          if (e != hipSuccess) return fail(VW_ERR_DEVICE, "round-trip launch failed: %s", hipGetErrorString(e));
+        }
+        if (flags & VW_FLAG_SYNC) VW_HIP(hipStreamSynchronize(c->stream));
+        return ok();
+      }
+      (void)hipGetLastError();
+    }
+  }
+  // the two calls, with their own argument checks
+  VW_TRY(modwt_forward<double>(c, x, B, N, ldx, lo, hi, L, wid, boundary, J, flags, details, approx));
+  return modwt_inverse<double>(c, details, approx, B, N, rlo, rhi, L, wid, boundary, J, ~0u, 0, flags, y);
+}
+
+extern "C" vw_status vw_roundtrip_occupancy(vw_ctx* c, int64_t N, int L, int J, unsigned flags, int* per_cu) {
+  if (!c || !per_cu) return fail(VW_ERR_NULL, "null argument");
+  *per_cu = 0;
+  if (N <= 0 || N > (1LL << 30) || L < 1 || L > kPairMaxTaps || J < 1 || J > kMaxLevels) return ok();
+  std::lock_guard<std::recursive_mutex> g(c->mu);
+  if (c->capturing) return fail(VW_ERR_STATE, "occupancy queries cannot be captured");
+  hipSetDevice(c->device);
+  // the planner reads a pointer's alignment and nothing behind it
+  double* const aligned = reinterpret_cast<double*>(uintptr_t(4096));
+  static const double taps[kPairMaxTaps] = {0};
+  FwdCall<double> fk;
+  fk.x = aligned; fk.details = aligned; fk.approx = aligned;
+  fk.B = 4LL * c->cus; fk.N = N; fk.ldx = N; fk.lo = taps; fk.hi = taps; fk.L = L; fk.J = J;
+  fk.flags = flags & VW_FLAG_FMA; fk.cus = c->cus;
+  FwdPlan<double> fp;
+  plan_forward(c->tune, fk, &fp);
+  if (fp.error != VW_OK || !pair_forward_shape(fp)) return ok();
+  if (pair_prepare(fp.args.taps, fp.fma, fp.threads, fp.lds, per_cu) != hipSuccess) {
+    (void)hipGetLastError();
+    *per_cu = 0;
+  }
+  return ok();
 }
 
 // Biorthogonal banks (BiorthogonalSpline / ReverseBiorthogonalSpline): lo has Llo taps, hi has Lhi.  Equal

@@ -861,18 +861,24 @@ __device__ __forceinline__ void nf_flag_row(int* flag, long long b, T z) {
 }
 
 // NFP: probe the final approximation (nf: the row's accumulator, see nf_probe)
-template <typename T, int L, bool FMA, int NV, bool VALIDATE, bool NFP = false, bool FULL = false, int LH = L>
+// AUX: cache policy of the coefficient stores.  dkeep (k_roundtrip): where the level's detail vectors stay in
+// registers besides being stored, in areg's layout (nullptr: nowhere).
+// INSTRUCTION COUNT: in the FULL form a lane issues exactly one vector-memory store per store_vec below, i.e. NV per
+// level and 2 * NV at the level that also writes aout, and nothing else.  The counted vmcnt waits of
+// k_forward_persist and k_roundtrip (vw_pair.hip: its reload of d_{J-1} behind the lane's own stores) depend on it.
+template <typename T, int L, bool FMA, int NV, bool VALIDATE, bool NFP = false, bool FULL = false, int LH = L,
+          int AUX = VW_FWD_STORE_AUX>
 __device__ __forceinline__ void fwd_level(const FwdArgs<T>& p, const T* X, int nvec, const LevelDesc& lv, T* dout,
                                           T* aout, bool vec_ok, unsigned long long flat0, T (&areg)[NV][VT<T>::V],
-                                          T* nf = nullptr) {
+                                          T* nf = nullptr, T (*dkeep)[VT<T>::V] = nullptr) {
   constexpr int V = VT<T>::V;
   const int N = p.N;
   // (the validating form keeps the run-time-stride body: one level body per kernel is enough there)
   const int ct = VALIDATE ? 0 : p.level_ct;
   fwd_row<T, L, FMA, NV, FULL, LH>(X, nvec, lv.s, p.lo, p.hi, p.taps, ct, [&](int k, int w, const T (&al)[V], const T (&ah)[V]) {
     const int t0 = w * V;
-    store_vec<VW_FWD_STORE_AUX, FULL>(dout, t0, N, vec_ok, ah);
-    if (aout) store_vec<VW_FWD_STORE_AUX, FULL>(aout, t0, N, vec_ok, al);
+    store_vec<AUX, FULL>(dout, t0, N, vec_ok, ah);
+    if (aout) store_vec<AUX, FULL>(aout, t0, N, vec_ok, al);
     if constexpr (VALIDATE) {
       check_out<T>(1, p.bad, flat0, t0, N, ah);
       check_out<T>(1, p.bad, flat0, t0, N, al);
@@ -882,6 +888,10 @@ __device__ __forceinline__ void fwd_level(const FwdArgs<T>& p, const T* X, int n
     }
 #pragma unroll
     for (int e = 0; e < V; ++e) areg[k][e] = al[e];
+    if (dkeep) {
+#pragma unroll
+      for (int e = 0; e < V; ++e) dkeep[k][e] = ah[e];
+    }
   }, p.taps_hi);
 }
 
@@ -987,6 +997,8 @@ __device__ __forceinline__ void lds_dma16(unsigned lds, const void* g, bool nt) 
   }
 }
 
+// INSTRUCTION COUNT: under the full-slab contract (threads * NV == nvec, whole waves) a wave issues exactly NV of
+// these.  k_forward_persist's vmcnt(2 * NV) and k_roundtrip's vmcnt(3 * NV) / vmcnt(2 * NV) (vw_pair.hip) count on it.
 template <typename T>
 __device__ __forceinline__ void dma_row(T* buf, const T* __restrict__ src, int nvec, bool nt) {
   constexpr int V = VT<T>::V;

@@ -114,6 +114,21 @@ struct InvArgs {
   LevelDesc lv[kMaxLevels];
 };
 
+// Forward, then inverse of the same rows in one launch (vw_pair.hip k_roundtrip; fp64, L <= 8): the forward's
+// arguments as k_forward_persist takes them, and what the inverse half reads besides -- inverse_seq_plain's
+// share of an InvArgs (vw_plan.cpp pair_fusable: the spacings are the forward's, the level buffer is the
+// forward's region from its first element on).
+constexpr int kPairMaxTaps = 8;
+template <typename T>
+struct PairArgs {
+  FwdArgs<T> f;
+  T* y;                   // [B][N]
+  T ilo[kPairMaxTaps];    // reconstruction taps * 1/sqrt(2)
+  T ihi[kPairMaxTaps];
+  int hr[kMaxLevels];     // InvArgs::lv[j].hr / .own
+  int own[kMaxLevels];
+};
+
 // Per-level tiled fallback (N too large for the fused kernels): one launch per level.
 template <typename T>
 struct LevelArgs {
@@ -369,6 +384,18 @@ template <typename T>
 hipError_t launch_forward_blk(const FwdArgs<T>& a, int threads, int lds_bytes, bool fma, int nv, hipStream_t st);
 template <typename T>
 hipError_t launch_inverse_fused(const InvArgs<T>& a, int threads, int lds_bytes, bool fma, int nv, hipStream_t st);
+// k_roundtrip (vw_pair.hip).  pair_prepare raises the kernel's dynamic-LDS limit and queries its occupancy (per_cu:
+// resident workgroups per CU, may be null): neither can be recorded, so the executor calls it where an eligible
+// forward runs uncaptured.  pair_launch_shape gives the launch of a prepared (taps, mode, threads, lds) -- the
+// host function, the resident grid -- and false for one that is not prepared on the current device; it makes no
+// call a capture forbids.
+struct PairLaunch {
+  const void* func;
+  unsigned grid, threads, lds;
+};
+hipError_t pair_prepare(int taps, bool fma, int threads, int lds_bytes, int* per_cu);
+bool pair_launch_shape(int taps, bool fma, int threads, int lds_bytes, long long B, int cus, PairLaunch* out);
+hipError_t launch_roundtrip(const PairArgs<double>& a, const PairLaunch& l, hipStream_t st);
 template <typename T>
 hipError_t launch_forward_level(const LevelArgs<T>& a, int lds_bytes, bool fma, hipStream_t st);
 template <typename T>

@@ -63,6 +63,7 @@ static const TuningKey kTuningTable[] = {
     VW_KEY("VW_BI", t.bi = v < 0 ? d.bi : v & 7),
     VW_KEY("VW_BI_LISTED", t.bi_listed = v < 0 ? d.bi_listed : v != 0),
     VW_KEY("VW_INV_WAVES", t.inv_waves = v == 6 || v == 8 ? v : d.inv_waves),
+    VW_KEY("VW_PAIR_FUSE", t.pair_fuse = v < 0 ? d.pair_fuse : v != 0),
 };
 #undef VW_KEY
 
@@ -807,6 +808,22 @@ static void inverse_levels(const InvCall<T>& c, int Llo, int Lhi, LevelDesc* lv,
   }
 }
 
+// The PLAIN class of inverse calls (vw_device.h inverse_seq_plain): a full-slab fp64 PERIODIC reconstruction of a short
+// filter from every coefficient plane, forward walk, no threshold, no probe -- every level reads t + i*s with no
+// left halo and a right one within the row.  Independent of the LDS buffer count: plan_inverse_fused marks
+// k_inverse_seq plans of the class (InvArgs::plain), pair_fusable also takes k_inverse_db plans of it.  Reads
+// a.full / a.rev / a.lv and p.ref_nf: call once those are set.
+template <typename T>
+static bool plain_class(const InvCall<T>& c, const InvPlan<T>& p, int nv) {
+  const InvArgs<T>& a = p.args;
+  if (!(a.full && sizeof(T) == 8 && nv == 4 && c.L <= 8 && c.boundary == VW_PERIODIC && !c.thr && !c.approx_zero &&
+        !a.rev && !p.ref_nf))
+    return false;
+  for (int j = 0; j < c.J; ++j)
+    if (!(a.lv[j].use_d && plus_zero(a.lv[j]) && a.lv[j].hl == 0 && a.lv[j].hr <= c.N)) return false;
+  return true;
+}
+
 // Fused inverse: one launch for all levels.  Returns false when the signal does not fit (per-level path).
 //
 // Pairwise sums need a_j and d_j together (two regions).  Sequential sums time-share one region
@@ -885,11 +902,7 @@ static bool plan_inverse_fused(const Tuning& tu, const InvCall<T>& c, bool pair,
   p->nf_probed = p->ref_nf && (p->kernel == kInvSeq || p->kernel == kInvBlk);
   // k_inverse_seq's PLAIN form (vw_device.h inverse_seq_plain; fp64 short filters, vw_inv.hip's dispatch): a
   // full-slab PERIODIC reconstruction that uses none of the general form's optional state
-  bool plain = a.full && p->kernel == kInvSeq && sizeof(T) == 8 && nv == 4 && L <= 8 && periodic && !c.thr &&
-               !c.approx_zero && !a.rev && !p->ref_nf;
-  for (int j = 0; plain && j < J; ++j)
-    plain = a.lv[j].use_d && plus_zero(a.lv[j]) && a.lv[j].hl == 0 && a.lv[j].hr <= N;
-  a.plain = plain ? 1 : 0;
+  a.plain = p->kernel == kInvSeq && plain_class(c, *p, nv) ? 1 : 0;
   a.waves = tu.inv_waves;
   p->threads = threads; p->nv = nv; p->lds = lds;
   return true;
@@ -1165,6 +1178,53 @@ void plan_inverse(const Tuning& tu, const InvCall<T>& c, InvPlan<T>* p) {
     plan_inverse_taps(tu, c, Lmax, p);
   }
 }
+
+// ------------------------------------------------------------------------------------------------
+// Forward -> inverse pairs (vw_plan.h pair_fusable).
+static bool ranges_overlap(const void* a, size_t a_bytes, const void* b, size_t b_bytes) {
+  const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
+  return a0 < b0 + b_bytes && b0 < a0 + a_bytes;
+}
+
+template <typename T>
+bool pair_fusable(const FwdCall<T>& fc, const FwdPlan<T>& fp, const InvCall<T>& ic, const InvPlan<T>& ip) {
+  if (sizeof(T) != 8) return false;
+  if (fp.error != VW_OK || ip.error != VW_OK || !fp.fused || !ip.fused) return false;
+  const int64_t B = fc.B, N = fc.N;
+  const int J = fc.J, L = fc.L;
+  // the two calls describe one round trip
+  if (ic.B != B || ic.N != N || ic.J != J || ic.L != L || hi_taps(fc) != L || hi_taps(ic) != L) return false;
+  if (fc.boundary != VW_PERIODIC || ic.boundary != VW_PERIODIC || fc.single_level || ic.single_level) return false;
+  if (fp.fma != ip.fma) return false;
+  if ((const T*)fc.details != ic.details || (const T*)fc.approx != ic.approx) return false;
+  const unsigned all = J >= 32 ? ~0u : (1u << J) - 1u;
+  if ((ic.detail_mask & all) != all || ic.approx_zero || ic.thr) return false;
+  const unsigned off = VW_FLAG_VALIDATE | VW_FLAG_REF_NONFINITE | VW_FLAG_HOST_MEMORY;
+  if ((fc.flags | ic.flags) & off) return false;
+  if (fc.hist || fp.validate || fp.ref_nf || ip.ref_nf || fp.snapshot) return false;
+  // the forward: k_forward_persist's full-slab form, a tap count k_roundtrip is instantiated for
+  if (fp.kernel != kFwdPersist || !fp.args.level_ct || fp.nv != 4 || fp.args.region1 <= 0) return false;
+  if (L > kPairMaxTaps || !has_unrolled_taps(L) || fp.args.taps != L || fp.args.taps_hi != L) return false;
+  // the inverse: the PLAIN class, in one buffer or in the two a small batch gets
+  const InvArgs<T>& ia = ip.args;
+  if (ip.threads != fp.threads || ip.nv != 4 || ia.taps != L || ia.taps_hi != L) return false;
+  if (!ia.plain && !(ip.kernel == kInvDb && plain_class(ic, ip, ip.nv))) return false;
+  // the inverse half works in a forward level region, from the region's first element on
+  for (int j = 0; j < J; ++j)
+    if (ia.lv[j].s != fp.args.lv[j].s || N + ia.lv[j].hr > fp.args.region1) return false;
+  if (fp.lds < 2 * fp.args.region1 * (int)sizeof(T)) return false;
+  // y is written while x and the coefficient planes of later rows are still to be read
+  const size_t row = (size_t)N * sizeof(T), plane = (size_t)B * row;
+  const size_t x_bytes = ((size_t)(B - 1) * (size_t)fc.ldx + (size_t)N) * sizeof(T);
+  if (ranges_overlap(ic.y, plane, fc.x, x_bytes) || ranges_overlap(ic.y, plane, fc.details, (size_t)J * plane) ||
+      ranges_overlap(ic.y, plane, fc.approx, plane))
+    return false;
+  return true;
+}
+template bool pair_fusable<float>(const FwdCall<float>&, const FwdPlan<float>&, const InvCall<float>&,
+                                  const InvPlan<float>&);
+template bool pair_fusable<double>(const FwdCall<double>&, const FwdPlan<double>&, const InvCall<double>&,
+                                   const InvPlan<double>&);
 
 template void plan_forward<float>(const Tuning&, const FwdCall<float>&, FwdPlan<float>*);
 template void plan_forward<double>(const Tuning&, const FwdCall<double>&, FwdPlan<double>*);

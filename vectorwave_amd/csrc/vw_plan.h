@@ -73,6 +73,8 @@ struct Tuning {
                                // faster than 6 on the db4 step (profiles/r09/ab_db4_inv_waves.log)
   int mra_fused = 1;           // VW_MRA_FUSED=0: vw_mra_planes_* / vw_modwt_mra_* never run k_mra (J+1 masked inverses instead);
                                // 2: k_mra wherever it fits, also where it measured slower than the loop (plan_mra)
+  int pair_fuse = 1;           // VW_PAIR_FUSE=0: a captured forward and the inverse that follows it stay two kernels;
+                               // 1: one k_roundtrip launch where pair_fusable holds (vw_capi.cpp)
   int bi_listed = 1;           // VW_BI_LISTED=0: a two-length bank runs max(Llo, Lhi) taps even where that count is not in
                                // VW_TAP_LIST (the runtime-L kernels); 1: one more zero tap where that reaches a listed count
 };
@@ -229,5 +231,21 @@ template <typename T> void plan_mra(const Tuning& tu, const InvCall<T>& c, MraPl
 // `p` must be a freshly constructed plan.
 template <typename T> void plan_forward(const Tuning& tu, const FwdCall<T>& c, FwdPlan<T>* p);
 template <typename T> void plan_inverse(const Tuning& tu, const InvCall<T>& c, InvPlan<T>* p);
+
+// Whether a forward call and the inverse call that follows it are one round trip that k_roundtrip (vw_pair.hip) computes
+// with the bits of the two kernels their plans name.  Pure: reads the calls and their plans, nothing behind a
+// pointer.  True only when
+//   - the forward plans to kFwdPersist in its full-slab form (fp64, NV = 4, a listed tap count <= kPairMaxTaps);
+//   - the inverse plans to the PLAIN class (InvArgs::plain), or to the two-buffer kernel small batches get
+//     (kInvDb) on a call that meets every condition of that class: the same sums in the same order;
+//   - both calls have the same B, N, J, tap count, PERIODIC boundary and accumulation mode, one filter length each;
+//   - the forward's details / approx (dense [J][B][N] and [B][N]) are the inverse's inputs;
+//   - the inverse keeps every level and the approximation, without a threshold;
+//   - neither call has VW_FLAG_VALIDATE, VW_FLAG_REF_NONFINITE or VW_FLAG_HOST_MEMORY;
+//   - y overlaps none of x, details, approx;
+//   - the inverse's right halos fit the forward's level regions (the kernel works in those).
+// Each call's own plan is what it was: the plan text (describe()) does not change.
+template <typename T>
+bool pair_fusable(const FwdCall<T>& fc, const FwdPlan<T>& fp, const InvCall<T>& ic, const InvPlan<T>& ip);
 
 }  // namespace vw

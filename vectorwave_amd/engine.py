@@ -224,6 +224,32 @@ class Engine:
                   detail_mask & 0xFFFFFFFF, 1 if approx_zero else 0, self._flags(flags, dev), self._ptr(y, dev)))
         return y
 
+    def roundtrip(self, x, lo, hi, rlo, rhi, wavelet_id: int, boundary: int, levels: int, flags: int):
+        """vw_modwt_roundtrip_f64: forward (lo, hi) then inverse (rlo, rhi) of x [B,N] (or [N]), float64 ->
+        (details, approx, y), the arrays of ``forward`` followed by ``inverse`` bit for bit; one launch where the
+        pair is eligible."""
+        xa, dev, xp, _ = self._prep(x, np.float64)
+        one = xa.ndim == 1
+        B, N = (1, xa.shape[0]) if one else xa.shape
+        det = self._empty(xa, dev, (levels, N) if one else (levels, B, N))
+        app = self._empty(xa, dev, xa.shape)
+        y = self._empty(xa, dev, xa.shape)
+        L = _one_length(lo, hi, "roundtrip")
+        if _one_length(rlo, rhi, "roundtrip") != L:
+            raise InvalidArgumentException("roundtrip takes one filter length for both pairs")
+        _check(self.lib.vw_modwt_roundtrip_f64(self.ctx, xp, B, N, N, nat.taps_array(lo), nat.taps_array(hi),
+                                               nat.taps_array(rlo), nat.taps_array(rhi), L, wavelet_id, boundary,
+                                               levels, self._flags(flags, dev), self._ptr(det, dev),
+                                               self._ptr(app, dev), self._ptr(y, dev)))
+        return det, app, y
+
+    def roundtrip_occupancy(self, N: int, L: int, levels: int, flags: int = 0) -> int:
+        """Resident workgroups per CU of the round-trip launch for rows of N samples (0: not eligible)."""
+        from ctypes import c_int
+        n = c_int()
+        _check(self.lib.vw_roundtrip_occupancy(self.ctx, int(N), int(L), int(levels), int(flags), byref(n)))
+        return n.value
+
     def forward1(self, x, lo, hi, boundary: int, flags: int):
         xa, dev, xp, f32 = self._prep(x, np.float64)
         one = xa.ndim == 1
@@ -462,6 +488,13 @@ class Graph:
 
     def launch(self, count: int = 1) -> None:
         _check(self.engine.lib.vw_graph_launch(self.handle, int(count)))
+
+    def stats(self) -> Tuple[int, int]:
+        """(kernel nodes, forward -> inverse pairs recorded as one round-trip launch) -- vw_graph_stats."""
+        from ctypes import c_int
+        k, f = c_int(), c_int()
+        _check(self.engine.lib.vw_graph_stats(self.handle, byref(k), byref(f)))
+        return k.value, f.value
 
     def close(self) -> None:
         if self.handle:
