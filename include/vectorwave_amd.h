@@ -327,6 +327,51 @@ VW_API vw_status vw_modwt_mra_f32(vw_ctx *ctx, const float *x, int64_t B, int64_
                                   const double *lo, const double *hi, int L, int wavelet_id, int boundary, int J,
                                   unsigned flags, float *out);
 
+/* ---- continuous wavelet transform ------------------------------------------------------------------
+ * CWTTransform.analyze (cwt/CWTTransform.java:71-79) for a batch of rows, table-driven: the caller tabulates the
+ * wavelet per scale, the GPU computes
+ *
+ *   out[b][s][tau] = ( sum_{k=0}^{K_s-1} w_s[k] * ext(x_b, tau + o_s + k) ) / q_s ,   tau in [0, N)
+ *
+ * with k ascending and ONE accumulator that starts at +0.0, the real (taps_re) and imaginary (taps_im) sums
+ * independent.  Without VW_FLAG_FMA multiply and add are separate roundings; with it each term is one fma.  The
+ * division is one IEEE division per output.  Every tap multiplies its sample, also a non-finite one, as the
+ * reference's loops do.
+ *   direct branch  analyzeDirect (:120-169) / analyzeDirectComplex (:174-218), t = -H..H ascending:
+ *                  w_s[k] = psi(-(k - H)/s) / sqrtScale, K_s = 2H + 1, o_s = -H, q_s = 1, ext = the padding strategy,
+ *                  H = max(16, ceil(8 s bandwidth)) / 2 (:774-794).
+ *   FFT branch     analyzeFFT (:223-318), real wavelets: w_s[k] = psi((k - H)/s), K_s = 2H + 1, o_s = +H (the
+ *                  extraction at i + halfSupport, :304-311: the window is NOT centred), q_s = sqrtScale,
+ *                  ext = VW_CWT_WRAP_ZERO with wrap = fftSize = nextPow2(N + maxSupport - 1) (:234-238).  The
+ *                  result is that branch's exact sum; the reference's FFT differs from it by its own rounding
+ *                  (~1e-15 relative).  Non-finite input is unspecified there: the reference's FFT spreads it over
+ *                  every output.
+ * scales[s] = {tap_begin, taps K_s, window_begin o_s, divisor q_s}: w_s[k] = taps_re[tap_begin + k] (and taps_im),
+ * tables of ntaps doubles on the HOST whatever the flags (rounded to float once by the _f32 call, the divisor
+ * too).  taps_im == NULL: real output, out_im is not written and may be NULL.  x is [B][ldx]; out_re / out_im are
+ * [B][S][N].  ext: VW_CWT_ZERO / REFLECT / SYMMETRIC / PERIODIC exactly as getBoundaryValue (:354-396), its clamps
+ * to N-1 and 0 for a window that overshoots by more than N included; VW_CWT_WRAP_ZERO reads index mod wrap, zero
+ * on [N, wrap).
+ * Flags: VW_FLAG_FMA, VW_FLAG_HOST_MEMORY, VW_FLAG_SYNC; any other is VW_ERR_ARG.
+ * Errors, all before any device work: null pointers VW_ERR_NULL; B, N or S = 0 VW_ERR_EMPTY; ldx < N, K_s < 1, a
+ * descriptor reaching outside [0, ntaps), q_s <= 0 (or NaN), |o_s| > 2^30, an unknown ext, wrap < 1 with
+ * WRAP_ZERO -> VW_ERR_ARG; K_s > 16384 -> VW_ERR_UNSUPPORTED naming the scale.
+ * The tables and descriptors are kept on the device between calls: a call with the same ones uploads nothing, and
+ * only such a call can be recorded into a vw_graph (VW_ERR_STATE otherwise).  Timing family: "cwt". */
+enum { VW_CWT_ZERO = 0, VW_CWT_REFLECT = 1, VW_CWT_SYMMETRIC = 2, VW_CWT_PERIODIC = 3, VW_CWT_WRAP_ZERO = 4 };
+typedef struct vw_cwt_scale {
+    int64_t tap_begin;
+    int32_t taps;
+    int32_t window_begin;
+    double divisor;
+} vw_cwt_scale;
+VW_API vw_status vw_cwt_f64(vw_ctx *ctx, const double *x, int64_t B, int64_t N, int64_t ldx,
+                            const vw_cwt_scale *scales, int S, const double *taps_re, const double *taps_im,
+                            int64_t ntaps, int ext, int64_t wrap, unsigned flags, double *out_re, double *out_im);
+VW_API vw_status vw_cwt_f32(vw_ctx *ctx, const float *x, int64_t B, int64_t N, int64_t ldx,
+                            const vw_cwt_scale *scales, int S, const double *taps_re, const double *taps_im,
+                            int64_t ntaps, int ext, int64_t wrap, unsigned flags, float *out_re, float *out_im);
+
 /* ---- one batch over several contexts (one host thread per context) ----------------------------
  * Replaces the reference's in-process parallelism over one batch call: BatchMODWT.multiLevelAoS /
  * inverseMultiLevelAoS (ext/extensions/modwt/BatchMODWT.java:90-111, :151-178) and the

@@ -140,6 +140,13 @@ public final class AmdNative {
     static native int mraPlanesAoS(long ctx, double[][][] details, double[][] approx, double[] lo, double[] hi,
                                    int waveletId, int boundary, int flags, double[] out);
 
+    // continuous wavelet transform of every signal (outRe / outIm: B * S * N doubles, [B][S][N]): scaleDesc holds
+    // {tap_begin, taps, window_begin} per scale, divisors one value per scale, tapsRe / tapsIm the flat tables (tapsIm
+    // and outIm null for a real wavelet); ext: CWT_ZERO .. CWT_WRAP_ZERO, wrap the period of CWT_WRAP_ZERO
+    public static final int CWT_ZERO = 0, CWT_REFLECT = 1, CWT_SYMMETRIC = 2, CWT_PERIODIC = 3, CWT_WRAP_ZERO = 4;
+    static native int cwtAoS(long ctx, double[][] rows, long[] scaleDesc, double[] divisors, double[] tapsRe,
+                             double[] tapsIm, int ext, long wrap, int flags, double[] outRe, double[] outIm);
+
     // com.morphiqlabs.financial: FinancialAnalyzer's four metrics + the detail standard deviation of every price
     // row (out: 5 * B doubles, [5][B]); FinancialWaveletAnalyzer's Sharpe ratios of every return row (out: B)
     static native int finAnalyzeAoS(long ctx, double[][] prices, double[] lo, double[] hi, double anomalyK, int flags,

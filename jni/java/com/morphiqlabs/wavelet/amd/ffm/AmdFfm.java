@@ -42,6 +42,8 @@ public final class AmdFfm implements AutoCloseable {
             devFree, memcpy, pipeCreate, pipeRun, pipeJoin, pipeDestroy;
     /** Declared only: vw_modwt_{forward,inverse}_bi_f64 for banks whose low-pass and high-pass differ in length. */
     private final MethodHandle forwardBi, inverseBi;
+    /** vw_cwt_f64: the continuous wavelet transform over host segments ({@link #cwtHost}). */
+    private final MethodHandle cwt;
     private final MemorySegment ctx;
 
     /** Loads {@code libvectorwave_amd.so} from {@code libraryPath} and creates a context on {@code device}. */
@@ -69,6 +71,9 @@ public final class AmdFfm implements AutoCloseable {
         inverseBi = fn("vw_modwt_inverse_bi_f64", FunctionDescriptor.of(JAVA_INT, ADDRESS, ADDRESS, ADDRESS, JAVA_LONG,
                 JAVA_LONG, ADDRESS, JAVA_INT, ADDRESS, JAVA_INT, JAVA_INT, JAVA_INT, JAVA_INT, JAVA_INT, JAVA_INT,
                 JAVA_INT, ADDRESS));
+        // vw_cwt_f64(ctx, x, B, N, ldx, scales, S, taps_re, taps_im, ntaps, ext, wrap, flags, out_re, out_im)
+        cwt = fn("vw_cwt_f64", FunctionDescriptor.of(JAVA_INT, ADDRESS, ADDRESS, JAVA_LONG, JAVA_LONG, JAVA_LONG, ADDRESS,
+                JAVA_INT, ADDRESS, ADDRESS, JAVA_LONG, JAVA_INT, JAVA_LONG, JAVA_INT, ADDRESS, ADDRESS));
         // vw_swt_denoise_f64(ctx, x, B, N, ldx, lo, hi, L, wavelet_id, boundary, J, threshold, soft, flags, y, thr)
         denoise = fn("vw_swt_denoise_f64", FunctionDescriptor.of(JAVA_INT, ADDRESS, ADDRESS, JAVA_LONG, JAVA_LONG,
                 JAVA_LONG, ADDRESS, ADDRESS, JAVA_INT, JAVA_INT, JAVA_INT, JAVA_INT, ValueLayout.JAVA_DOUBLE, JAVA_INT,
@@ -125,6 +130,35 @@ public final class AmdFfm implements AutoCloseable {
         try (Arena a = Arena.ofConfined()) {
             check((int) inverse.invokeExact(ctx, details, approx, B, N, taps(a, lo), taps(a, hi), lo.length, waveletId,
                     boundary, J, -1, 0, flags | FLAG_HOST_MEMORY | FLAG_SYNC, y));
+        } catch (Throwable t) {
+            throw rethrow(t);
+        }
+    }
+
+    /**
+     * CWTTransform.analyze over host segments: x [B][N] -> outRe / outIm [B][S][N].  Scale s reads
+     * {@code taps[s]} values from {@code tapBegin[s]} of the flat tables, its window starts at {@code tau + windowBegin[s]}
+     * and its sums are divided by {@code divisors[s]} (vw_cwt_scale; AmdCWTTransform builds them).  tapsIm and outIm
+     * null: a real wavelet.
+     */
+    public void cwtHost(MemorySegment x, long B, long N, long[] tapBegin, int[] taps, int[] windowBegin, double[] divisors,
+                        double[] tapsRe, double[] tapsIm, int ext, long wrap, int flags, MemorySegment outRe,
+                        MemorySegment outIm) {
+        final int S = divisors.length;
+        requireBytes(x, B * N, "x");
+        requireBytes(outRe, B * S * N, "outRe");
+        if (tapsIm != null) requireBytes(outIm, B * S * N, "outIm");
+        try (Arena a = Arena.ofConfined()) {
+            MemorySegment sc = a.allocate(24L * S, 8);   // vw_cwt_scale: int64, int32, int32, double
+            for (int s = 0; s < S; s++) {
+                sc.set(JAVA_LONG, 24L * s, tapBegin[s]);
+                sc.set(JAVA_INT, 24L * s + 8, taps[s]);
+                sc.set(JAVA_INT, 24L * s + 12, windowBegin[s]);
+                sc.set(ValueLayout.JAVA_DOUBLE, 24L * s + 16, divisors[s]);
+            }
+            check((int) cwt.invokeExact(ctx, x, B, N, N, sc, S, taps(a, tapsRe),
+                    tapsIm == null ? MemorySegment.NULL : taps(a, tapsIm), (long) tapsRe.length, ext, wrap,
+                    flags | FLAG_HOST_MEMORY | FLAG_SYNC, outRe, tapsIm == null ? MemorySegment.NULL : outIm));
         } catch (Throwable t) {
             throw rethrow(t);
         }

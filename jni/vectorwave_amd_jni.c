@@ -813,6 +813,62 @@ JNIEXPORT jint JNICALL VW_JNI(mraPlanesAoS)(JNIEnv *e, jclass c, jlong ctx, jobj
   return st;
 }
 
+/* ---- continuous wavelet transform: outRe / outIm = B * S * N doubles, [B][S][N] ----
+ * signals double[B][N]; scaleDesc long[3 S] = {tap_begin, taps, window_begin} per scale and divisors double[S] (the
+ * fields of vw_cwt_scale); tapsRe / tapsIm the flat tables (tapsIm null: real output, outIm not read).  Row chunks as
+ * mraAoS: a chunk's [nb][S][N] planes are rows b0 .. b0+nb of the caller's flat arrays, which must fit a Java
+ * array.  The tables are copied once per call; the context keeps them on the device from chunk to chunk. */
+JNIEXPORT jint JNICALL VW_JNI(cwtAoS)(JNIEnv *e, jclass c, jlong ctx, jobjectArray x, jlongArray scaleDesc,
+                                      jdoubleArray divisors, jdoubleArray tapsRe, jdoubleArray tapsIm, jint ext,
+                                      jlong wrap, jint flags, jdoubleArray outRe, jdoubleArray outIm) {
+  (void)c;
+  if (!scaleDesc || !divisors) return null_error(e, "Scales cannot be null");
+  if (!tapsRe) return null_error(e, "wavelet tables cannot be null");
+  const jsize S = (*e)->GetArrayLength(e, divisors);
+  if (S < 1) return arg_error(e, "Scales cannot be empty");
+  if ((*e)->GetArrayLength(e, scaleDesc) != 3 * S) return arg_error(e, "scaleDesc must hold 3 values per scale");
+  const jsize ntaps = (*e)->GetArrayLength(e, tapsRe);
+  if (ntaps < 1 || (tapsIm && (*e)->GetArrayLength(e, tapsIm) != ntaps))
+    return arg_error(e, "wavelet tables must be non-empty and of one length");
+  const jsize N = row_len(e, x);
+  if (N < 1) return VW_ERR_ARG;
+  const jsize B = (*e)->GetArrayLength(e, x);
+  const size_t need = (size_t)B * (size_t)S * (size_t)N;
+  if (need > (size_t)0x7fffffff) return arg_error(e, "batch * scales * length exceeds a Java array");
+  if (!fin_out_ok(e, outRe, need) || (tapsIm && !fin_out_ok(e, outIm, need))) return VW_ERR_ARG;
+  const jsize CB = chunk_rows(((size_t)(tapsIm ? 2 : 1) * S + 1) * (size_t)N, B);
+  int oom = 0;
+  double *px = out_buf(0, (size_t)CB * N, &oom), *pre = out_buf(1, (size_t)CB * S * N, &oom);
+  double *pim = tapsIm ? out_buf(2, (size_t)CB * S * N, &oom) : NULL;
+  vw_cwt_scale *sc = (vw_cwt_scale *)malloc((size_t)S * sizeof(vw_cwt_scale));
+  jlong *ld = (jlong *)malloc((size_t)3 * S * sizeof(jlong));
+  double *tab = (double *)malloc(((size_t)(tapsIm ? 2 : 1) * ntaps + S) * sizeof(double));
+  if (oom || !sc || !ld || !tab) { free(sc); free(ld); free(tab); return oom_error(e); }
+  double *tre = tab, *tim = tapsIm ? tab + ntaps : NULL, *q = tab + (size_t)(tapsIm ? 2 : 1) * ntaps;
+  (*e)->GetLongArrayRegion(e, scaleDesc, 0, 3 * S, ld);
+  (*e)->GetDoubleArrayRegion(e, divisors, 0, S, q);
+  (*e)->GetDoubleArrayRegion(e, tapsRe, 0, ntaps, tre);
+  if (tapsIm) (*e)->GetDoubleArrayRegion(e, tapsIm, 0, ntaps, tim);
+  vw_status st = VW_OK;
+  for (jsize s = 0; s < S; ++s) {
+    const jlong k = ld[3 * s + 1], o = ld[3 * s + 2];
+    if (k < 1 || k > 0x7fffffff || o > 0x7fffffff || o < -0x7fffffff) { st = arg_error(e, "scale descriptor out of range"); break; }
+    sc[s].tap_begin = ld[3 * s]; sc[s].taps = (int32_t)k; sc[s].window_begin = (int32_t)o; sc[s].divisor = q[s];
+  }
+  for (jsize b0 = 0; b0 < B && st == VW_OK; b0 += CB) {
+    const jsize nb = B - b0 < CB ? B - b0 : CB;
+    if (!gather_rows(e, x, b0, nb, N, px)) { st = VW_ERR_ARG; break; }
+    st = vw_cwt_f64(CTX(ctx), px, nb, N, N, sc, S, tre, tim, ntaps, ext, wrap, (unsigned)flags | HOST_FLAGS, pre, pim);
+    if (st != VW_OK) break;
+    const jsize at = (jsize)((size_t)b0 * S * N), cnt = (jsize)((size_t)nb * S * N);
+    (*e)->SetDoubleArrayRegion(e, outRe, at, cnt, pre);
+    if (tapsIm) (*e)->SetDoubleArrayRegion(e, outIm, at, cnt, pim);
+  }
+  free(sc); free(ld); free(tab);
+  trim_slots();
+  return st;
+}
+
 /* lo == NULL: vw_fin_sharpe_f64; else vw_fin_wavelet_sharpe_f64 */
 static jint fin_sharpe_rows(JNIEnv *e, jlong ctx, jobjectArray returns, const Taps *tl, const Taps *th, jint boundary,
                             jdouble riskFree, jint flags, jdoubleArray out) {

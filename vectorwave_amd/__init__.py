@@ -12,6 +12,8 @@ include/vectorwave_amd.h).  This package is the host-side mirror of the referenc
   BatchMODWT, BatchStreamingMODWT                             (ext/extensions/modwt)
   Haar, Daubechies, Symlet, Coiflet, BiorthogonalSpline,
   ReverseBiorthogonalSpline                                   (core/api wavelets)
+  CWTTransform, CWTConfig, CWTResult, ScaleSpace, MorletWavelet,
+  RickerWavelet, PaulWavelet, DOGWavelet                      (core/cwt, core/cwt/finance)
 """
 from .wavelets import (BiorthogonalSpline, BiorthogonalWavelet, Coiflet, Daubechies, Haar, ReverseBiorthogonalSpline,
                        Symlet, Wavelet, available_wavelets, get_wavelet)
@@ -28,6 +30,8 @@ from .financial import (FinancialAnalysisConfig, FinancialAnalyzer, FinancialCon
                         VolatilityClassification)
 from .engine import Engine, max_levels, version
 from .multidevice import DeviceGroup
+from .cwt import (ComplexContinuousWavelet, ContinuousWavelet, CWTConfig, CWTResult, CWTTransform, DOGWavelet,
+                  MorletWavelet, PaddingStrategy, PaulWavelet, RickerWavelet, ScaleSpace)
 
 __all__ = [
     "Coiflet", "Daubechies", "Haar", "Symlet", "Wavelet", "available_wavelets", "get_wavelet",
@@ -39,4 +43,6 @@ __all__ = [
     "BatchStreamingMODWT", "Engine", "max_levels", "version", "DeviceGroup",
     "FinancialAnalysisConfig", "FinancialAnalyzer", "FinancialConfig", "FinancialWaveletAnalyzer",
     "VolatilityClassification", "BiorthogonalSpline", "BiorthogonalWavelet", "ReverseBiorthogonalSpline",
+    "ComplexContinuousWavelet", "ContinuousWavelet", "CWTConfig", "CWTResult", "CWTTransform", "DOGWavelet",
+    "MorletWavelet", "PaddingStrategy", "PaulWavelet", "RickerWavelet", "ScaleSpace",
 ]

@@ -27,6 +27,14 @@ FLAG_TREE_SUMS = 1 << 9
 
 PERIODIC, SYMMETRIC, ZERO_PADDING = 0, 1, 2
 
+# continuous wavelet transform: extensions and the per-scale descriptor (vw_cwt_scale)
+CWT_ZERO, CWT_REFLECT, CWT_SYMMETRIC, CWT_PERIODIC, CWT_WRAP_ZERO = 0, 1, 2, 3, 4
+
+
+class CwtScale(ctypes.Structure):
+    _fields_ = [("tap_begin", c_int64), ("taps", ctypes.c_int32), ("window_begin", ctypes.c_int32),
+                ("divisor", c_double)]
+
 # Every symbol include/vectorwave_amd.h declares, with its ctypes signature.
 _dp = POINTER(c_double)
 _fp = POINTER(c_float)
@@ -92,6 +100,11 @@ SIGNATURES = {
                                  c_int, c_uint, c_void_p]),
     "vw_modwt_mra_f32": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int64, _dp, _dp, c_int, c_int, c_int,
                                  c_int, c_uint, c_void_p]),
+    # continuous wavelet transform: (scales, S, taps_re, taps_im, ntaps, ext, wrap), out_re / out_im [B][S][N]
+    "vw_cwt_f64": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int64, POINTER(CwtScale), c_int, _dp, _dp, c_int64,
+                           c_int, c_int64, c_uint, c_void_p, c_void_p]),
+    "vw_cwt_f32": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int64, POINTER(CwtScale), c_int, _dp, _dp, c_int64,
+                           c_int, c_int64, c_uint, c_void_p, c_void_p]),
     "vw_fin_analyze_f64": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int64, _dp, _dp, c_int, c_double, c_uint,
                                    c_void_p]),
     "vw_fin_sharpe_f64": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int64, c_double, c_uint, c_void_p]),

@@ -106,6 +106,9 @@ struct vw_ctx {
   int64_t nf_rows = 0;
   PairPending pair;            // VW_PAIR_FUSE: the forward the next call may fuse with (capture only)
   int fused_pairs = 0;         // round trips recorded by the current capture
+  void* cwt_dev = nullptr;     // vw_cwt_*: the scale descriptors and tap tables of the last call, on the device
+  size_t cwt_dev_bytes = 0;
+  std::vector<unsigned char> cwt_img;  // ... and the host image they were copied from (a call with the same one uploads nothing)
 };
 
 struct vw_graph {
@@ -330,6 +333,7 @@ extern "C" vw_status vw_ctx_destroy(vw_ctx* c) {
   if (c->ws2) hipFree(c->ws2);
   if (c->med) hipFree(c->med);
   if (c->nf) hipFree(c->nf);
+  if (c->cwt_dev) hipFree(c->cwt_dev);
   for (auto& b : c->stage) hipFree(b.first);
   if (c->bad) hipFree(c->bad);
   if (c->own_stream) hipStreamDestroy(c->stream);
@@ -2239,6 +2243,143 @@ extern "C" vw_status vw_modwt_mra_f32(vw_ctx* c, const float* x, int64_t B, int6
                                       const double* hi, int L, int wid, int boundary, int J, unsigned flags,
                                       float* out) {
   return modwt_mra<float>(c, x, B, N, ldx, lo, hi, L, wid, boundary, J, flags, out);
+}
+
+// ------------------------------------------------------------------------------------------------
+// Continuous wavelet transform (vw_cwt.hip): fixed-order correlations of each row with one table per scale, plan_cwt's
+// launches heaviest scales first.  Timing family: "cwt".
+
+// The call's device image: [CwtScaleDev x S, plan order][taps_re x ntaps][taps_im x ntaps], T-typed, 16-byte aligned
+// parts.  Kept in the context: the same image again uploads nothing.  A new one bumps ws_gen (graphs recorded on
+// the old tables are stale) and cannot be recorded.
+template <typename T>
+static vw_status cwt_upload(vw_ctx* c, const CwtPlan& p, const vw_cwt_scale* scales, int S, const double* taps_re,
+                            const double* taps_im, int64_t ntaps, const CwtScaleDev<T>** sc, const T** dre,
+                            const T** dim) {
+  const size_t sc_bytes = align_up((size_t)S * sizeof(CwtScaleDev<T>), 16);
+  const size_t tab_bytes = align_up((size_t)ntaps * sizeof(T), 16);
+  const size_t bytes = sc_bytes + tab_bytes * (taps_im ? 2 : 1);
+  std::vector<unsigned char> img(bytes + 2, 0);
+  img[bytes] = (unsigned char)sizeof(T);  // the layout's own parameters close the image
+  img[bytes + 1] = taps_im ? 1 : 0;
+  CwtScaleDev<T>* hs = reinterpret_cast<CwtScaleDev<T>*>(img.data());
+  for (int i = 0; i < S; ++i) {
+    const vw_cwt_scale& d = scales[p.order[i].scale];
+    CwtScaleDev<T> e;
+    std::memset(&e, 0, sizeof(e));  // the image is compared byte for byte, padding included
+    e.tap_begin = (int)d.tap_begin; e.taps = d.taps; e.window = d.window_begin; e.scale = p.order[i].scale;
+    e.divisor = (T)d.divisor;
+    std::memcpy(&hs[i], &e, sizeof(e));
+  }
+  T* hre = reinterpret_cast<T*>(img.data() + sc_bytes);
+  for (int64_t i = 0; i < ntaps; ++i) hre[i] = (T)taps_re[i];
+  if (taps_im) {
+    T* him = reinterpret_cast<T*>(img.data() + sc_bytes + tab_bytes);
+    for (int64_t i = 0; i < ntaps; ++i) him[i] = (T)taps_im[i];
+  }
+  if (img != c->cwt_img) {
+    if (c->capturing) return fail(VW_ERR_STATE, "vw_cwt: new tables cannot be uploaded during a capture (run the call once first)");
+    if (c->cwt_dev_bytes < bytes) {
+      VW_HIP(hipStreamSynchronize(c->stream));
+      if (c->cwt_dev) hipFree(c->cwt_dev);
+      c->cwt_dev = nullptr; c->cwt_dev_bytes = 0; c->cwt_img.clear();
+      VW_HIP(hipMalloc(&c->cwt_dev, bytes));
+      c->cwt_dev_bytes = bytes;
+    }
+    c->cwt_img.clear();  // (not valid until the copy is enqueued)
+    VW_HIP(hipMemcpyAsync(c->cwt_dev, img.data(), bytes, hipMemcpyHostToDevice, c->stream));
+    VW_HIP(hipStreamSynchronize(c->stream));  // img is this call's
+    c->cwt_img.swap(img);
+    ++c->ws_gen;
+  }
+  const unsigned char* base = static_cast<const unsigned char*>(c->cwt_dev);
+  *sc = reinterpret_cast<const CwtScaleDev<T>*>(base);
+  *dre = reinterpret_cast<const T*>(base + sc_bytes);
+  *dim = taps_im ? reinterpret_cast<const T*>(base + sc_bytes + tab_bytes) : nullptr;
+  return VW_OK;
+}
+
+template <typename T>
+static vw_status cwt_impl(vw_ctx* c, const T* x, int64_t B, int64_t N, int64_t ldx, const vw_cwt_scale* scales, int S,
+                          const double* taps_re, const double* taps_im, int64_t ntaps, int ext, int64_t wrap,
+                          unsigned flags, T* out_re, T* out_im) {
+  if (!c) return fail(VW_ERR_NULL, "ctx is null");
+  if (!x || !scales || !taps_re || !out_re || (taps_im && !out_im)) return fail(VW_ERR_NULL, "null array argument");
+  if (B <= 0) return fail(VW_ERR_EMPTY, "batch must be non-empty (B=%lld)", (long long)B);
+  if (N <= 0) return fail(VW_ERR_EMPTY, "Signal cannot be empty");
+  if (S <= 0) return fail(VW_ERR_EMPTY, "Scales cannot be empty");
+  if (N > (1LL << 30)) return fail(VW_ERR_ARG, "signal length %lld too large", (long long)N);
+  if (ldx < N) return fail(VW_ERR_ARG, "ldx (%lld) < N (%lld)", (long long)ldx, (long long)N);
+  if (flags & ~(unsigned)(VW_FLAG_FMA | VW_FLAG_HOST_MEMORY | VW_FLAG_SYNC))
+    return fail(VW_ERR_ARG, "vw_cwt takes FMA, HOST_MEMORY and SYNC only");
+  if (ext < VW_CWT_ZERO || ext > VW_CWT_WRAP_ZERO) return fail(VW_ERR_ARG, "unknown extension %d", ext);
+  if (ext == VW_CWT_WRAP_ZERO && wrap < 1) return fail(VW_ERR_ARG, "VW_CWT_WRAP_ZERO needs wrap >= 1 (wrap=%lld)", (long long)wrap);
+  if (ntaps < 1 || ntaps > (1LL << 30)) return fail(VW_ERR_ARG, "ntaps (%lld) outside 1..2^30", (long long)ntaps);
+  std::vector<int> K((size_t)S);
+  for (int s = 0; s < S; ++s) {
+    const vw_cwt_scale& d = scales[s];
+    if (d.taps < 1) return fail(VW_ERR_ARG, "scale %d has %d taps", s, (int)d.taps);
+    if (d.tap_begin < 0 || d.tap_begin > ntaps - d.taps)
+      return fail(VW_ERR_ARG, "scale %d reads taps [%lld, %lld) outside the table of %lld", s, (long long)d.tap_begin,
+                  (long long)d.tap_begin + d.taps, (long long)ntaps);
+    if (!(d.divisor > 0.0) || !((T)d.divisor > (T)0) || std::isinf((T)d.divisor))
+      return fail(VW_ERR_ARG, "scale %d has divisor %g (must be positive and finite)", s, d.divisor);
+    if (d.window_begin > (1 << 30) || d.window_begin < -(1 << 30))
+      return fail(VW_ERR_ARG, "scale %d has window_begin %d outside +-2^30", s, (int)d.window_begin);
+    K[s] = d.taps;
+  }
+  CwtCall k;
+  k.B = B; k.N = N; k.S = S; k.taps = K.data(); k.elem_bytes = (int)sizeof(T); k.cplx = taps_im != nullptr; k.ext = ext;
+  k.flags = flags;
+  CwtPlan p;
+  plan_cwt(k, &p);
+  if (p.error != VW_OK) return fail((vw_status)p.error, "%s", p.msg);
+
+  std::lock_guard<std::recursive_mutex> g(c->mu);
+  hipSetDevice(c->device);
+  VW_TRY(capture_guard(c, flags));
+  CwtArgs<T> a{};
+  VW_TRY(cwt_upload<T>(c, p, scales, S, taps_re, taps_im, ntaps, &a.sc, &a.taps_re, &a.taps_im));
+  const CwtScaleDev<T>* const sc0 = a.sc;
+  a.ldx = ldx; a.B = B; a.N = (int)N; a.S = S; a.ntiles = p.ntiles; a.ext = ext; a.wrap = wrap > 0 ? wrap : 1;
+  const size_t planes = (size_t)B * (size_t)S * (size_t)N;
+  auto launches = [&]() -> vw_status {
+    for (const CwtLaunch& l : p.launches) {
+      a.sc = sc0 + l.first; a.nsc = l.count;
+      LaunchTimer lt(c, "cwt");
+      hipError_t e = launch_cwt<T>(a, p.threads, l.lds, p.cplx, p.fma, l.grid, c->stream);
+      if (e != hipSuccess) return fail(VW_ERR_DEVICE, "cwt launch failed: %s", hipGetErrorString(e));
+    }
+    return VW_OK;
+  };
+  if (flags & VW_FLAG_HOST_MEMORY) {
+    Staging stg(c);
+    T *dx, *dre, *dim = nullptr;
+    VW_TRY(stg.in(x, (size_t)(B - 1) * ldx + N, &dx));  // (the last row's padding need not exist)
+    VW_TRY(stg.in<T>(nullptr, planes, &dre));
+    if (taps_im) VW_TRY(stg.in<T>(nullptr, planes, &dim));
+    a.x = dx; a.out_re = dre; a.out_im = dim;
+    VW_TRY(launches());
+    VW_TRY(stg.out(out_re, dre, planes));
+    if (taps_im) VW_TRY(stg.out(out_im, dim, planes));
+    VW_HIP(hipStreamSynchronize(c->stream));
+    return ok();
+  }
+  a.x = x; a.out_re = out_re; a.out_im = taps_im ? out_im : nullptr;
+  VW_TRY(launches());
+  if (flags & VW_FLAG_SYNC) VW_HIP(hipStreamSynchronize(c->stream));
+  return ok();
+}
+
+extern "C" vw_status vw_cwt_f64(vw_ctx* c, const double* x, int64_t B, int64_t N, int64_t ldx, const vw_cwt_scale* scales,
+                                int S, const double* taps_re, const double* taps_im, int64_t ntaps, int ext, int64_t wrap,
+                                unsigned flags, double* out_re, double* out_im) {
+  return cwt_impl<double>(c, x, B, N, ldx, scales, S, taps_re, taps_im, ntaps, ext, wrap, flags, out_re, out_im);
+}
+extern "C" vw_status vw_cwt_f32(vw_ctx* c, const float* x, int64_t B, int64_t N, int64_t ldx, const vw_cwt_scale* scales,
+                                int S, const double* taps_re, const double* taps_im, int64_t ntaps, int ext, int64_t wrap,
+                                unsigned flags, float* out_re, float* out_im) {
+  return cwt_impl<float>(c, x, B, N, ldx, scales, S, taps_re, taps_im, ntaps, ext, wrap, flags, out_re, out_im);
 }
 
 // ------------------------------------------------------------------------------------------------

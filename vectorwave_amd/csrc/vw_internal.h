@@ -352,6 +352,54 @@ struct MraArgs {
 template <typename T>
 hipError_t launch_mra(const MraArgs<T>& a, int threads, int lds_bytes, bool fma, int nv, int grid, hipStream_t st);
 
+// Continuous wavelet transform (vw_cwt.hip k_cwt): out[b][s][tau] = (sum_k w_s[k] * ext(x_b, tau + o_s + k)) / q_s,
+// k ascending from an accumulator at +0.0 -- CWTTransform.analyzeDirect / analyzeDirectComplex (:120-218) with the
+// table w_s[k] = psi(-(k - H)/s)/sqrt(s), o_s = -H, q_s = 1, and analyzeFFT (:223-318) as the shifted sum over the
+// zero-padded FFT period (kCwtWrapZero, o_s = +H, q_s = sqrt(s)).
+enum CwtExt : int {        // ext(x, i) outside [0, N): CWTTransform.getBoundaryValue :354-396
+  kCwtZero = 0,            // 0
+  kCwtReflect = 1,         // i < 0: x[min(-i, N-1)];      i >= N: x[max(2N - i - 2, 0)]
+  kCwtSymmetric = 2,       // i < 0: x[min(-i - 1, N-1)];  i >= N: x[max(2N - i - 1, 0)]
+  kCwtPeriodic = 3,        // x[((i % N) + N) % N]
+  kCwtWrapZero = 4         // m = i mod M: x[m] when m < N, else 0 (the FFT branch's zero-padded period M)
+};
+constexpr int kCwtChunkBytes = 32;  // a thread's NV adjacent outputs: 32 bytes of elements (NV = 4 fp64, 8 fp32)
+constexpr int kCwtThreads = 256;    // most threads of a k_cwt workgroup (tile = threads * NV outputs)
+constexpr int kCwtMaxTaps = 16384;  // longest table of one scale the planner places (Morlet at scale 2048)
+constexpr int kCwtMaxGrid = 1 << 20;  // workgroups per launch; the kernel strides over the work items beyond
+// Chunks of NV elements a workgroup stages for a scale of K taps, the one rule of the planner (LDS bytes =
+// chunks * kCwtChunkBytes) and the kernel: thread t reads chunks t .. t + K / NV + 1.  Odd, so that the two 16-byte
+// planes of the chunks (vw_cwt.hip cwt_slot) start on different halves of a 256-byte bank row.
+constexpr int cwt_chunks(int threads, int K, int nv) { return (threads + K / nv + 1) | 1; }
+// One scale as the kernel reads it (device memory, heaviest first), T-typed divisor.
+template <typename T>
+struct CwtScaleDev {
+  int tap_begin;   // first tap in taps_re / taps_im
+  int taps;        // K_s
+  int window;      // o_s
+  int scale;       // the caller's scale index (output plane)
+  T divisor;       // q_s
+};
+template <typename T>
+struct CwtArgs {
+  const T* x;                  // [B][ldx]
+  long long ldx;
+  T* out_re;                   // [B][S][N]
+  T* out_im;                   // [B][S][N], complex tables only
+  const T* taps_re;            // device tables, rounded to T once on the host
+  const T* taps_im;
+  const CwtScaleDev<T>* sc;    // the launch's scales
+  long long B;
+  int N;
+  int S;                       // scales of the whole call (the stride of a row's planes)
+  int nsc;                     // scales of this launch
+  int ntiles;                  // ceil(N / (threads * NV))
+  int ext;                     // CwtExt
+  long long wrap;              // M of kCwtWrapZero
+};
+template <typename T>
+hipError_t launch_cwt(const CwtArgs<T>& a, int threads, int lds_bytes, bool cplx, bool fma, int grid, hipStream_t st);
+
 // Raise a kernel's dynamic-LDS limit past the 64 KiB default once per kernel instantiation AND
 // device (the attribute belongs to the device's copy of the function; a call per launch costs host
 // time).  `once` is a static of the caller, unique per kernel instantiation; several host threads

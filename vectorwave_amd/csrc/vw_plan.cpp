@@ -1149,6 +1149,45 @@ void plan_mra(const Tuning& tu, const InvCall<T>& c, MraPlan<T>* p) {
 template void plan_mra<float>(const Tuning&, const InvCall<float>&, MraPlan<float>*);
 template void plan_mra<double>(const Tuning&, const InvCall<double>&, MraPlan<double>*);
 
+// ------------------------------------------------------------------------------------------------
+// Continuous wavelet transform (vw_plan.h CwtPlan)
+static int cwt_lds_class(int lds) {  // 0: up to 16 KiB, 1: up to 32 KiB, ...
+  int cls = 0;
+  for (int cap = 16 * 1024; cap < lds; cap *= 2) ++cls;
+  return cls;
+}
+
+void plan_cwt(const CwtCall& c, CwtPlan* p) {
+  p->fma = (c.flags & VW_FLAG_FMA) != 0;
+  p->cplx = c.cplx;
+  const int nv = kCwtChunkBytes / c.elem_bytes;
+  const int64_t want = ((c.N + nv - 1) / nv + 63) / 64 * 64;  // whole waves covering the row
+  const int threads = (int)std::min<int64_t>(want, kCwtThreads);
+  const int tile = threads * nv;
+  p->threads = threads; p->nv = nv; p->tile = tile;
+  p->ntiles = (int)((c.N + tile - 1) / tile);
+  for (int s = 0; s < c.S; ++s) {
+    const int K = c.taps[s];
+    if (K > kCwtMaxTaps) {
+      p->error = VW_ERR_UNSUPPORTED;
+      snprintf(p->msg, sizeof(p->msg), "scale %d has %d taps: more than the %d a workgroup stages", s, K, kCwtMaxTaps);
+      p->order.clear();
+      return;
+    }
+    const int chunks = cwt_chunks(threads, K, nv);
+    p->order.push_back(CwtScalePlan{s, K, tile, nv, threads, chunks, chunks * kCwtChunkBytes});
+  }
+  std::stable_sort(p->order.begin(), p->order.end(),
+                   [](const CwtScalePlan& a, const CwtScalePlan& b) { return a.taps > b.taps; });
+  for (int i = 0; i < c.S;) {
+    int n = 1;
+    while (i + n < c.S && cwt_lds_class(p->order[i + n].lds) == cwt_lds_class(p->order[i].lds)) ++n;
+    const int64_t work = (int64_t)n * p->ntiles * c.B;
+    p->launches.push_back(CwtLaunch{i, n, p->order[i].lds, (int)std::min<int64_t>(work, kCwtMaxGrid)});
+    i += n;
+  }
+}
+
 template <typename T>
 void plan_forward(const Tuning& tu, const FwdCall<T>& c, FwdPlan<T>* p) {
   const int Lmax = std::max(c.L, hi_taps(c)), taps = listed_taps(tu, Lmax, c.L != hi_taps(c));

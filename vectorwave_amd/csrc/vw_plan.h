@@ -213,6 +213,43 @@ struct MraPlan {
 };
 template <typename T> void plan_mra(const Tuning& tu, const InvCall<T>& c, MraPlan<T>* p);
 
+// vw_cwt_* (vw_cwt.hip k_cwt): the launch shape of a continuous wavelet transform.  One thread count for the call
+// -- whole waves covering the row in chunks of NV = 32 bytes / element size outputs, at most kCwtThreads -- hence one
+// tile length (threads * NV) and tile count.  Per scale: the staged chunks (cwt_chunks) and their LDS bytes.  The
+// scales run heaviest first (K descending, ties in the caller's order), in launches of neighbours whose LDS need
+// falls in the same power-of-two class from 16 KiB up, so a light scale keeps the occupancy a heavy one cannot have;
+// a launch's LDS is its first (heaviest) scale's.  A scale with K > kCwtMaxTaps is refused: error
+// VW_ERR_UNSUPPORTED, `msg` names it, nothing else of the plan is valid.
+struct CwtCall {
+  int64_t B = 0, N = 0;
+  int S = 0;
+  const int* taps = nullptr;  // K_s per scale (>= 1, checked by the caller)
+  int elem_bytes = 8;
+  bool cplx = false;
+  int ext = kCwtZero;
+  unsigned flags = 0;
+};
+struct CwtScalePlan {
+  int scale;            // the caller's index
+  int taps;
+  int tile, nv, threads;
+  int chunks, lds;      // staged chunks of nv elements; lds = chunks * kCwtChunkBytes
+};
+struct CwtLaunch {
+  int first, count;     // scales order[first .. first + count)
+  int lds;
+  int grid;             // workgroups: min(count * ntiles * B, kCwtMaxGrid)
+};
+struct CwtPlan {
+  int error = VW_OK;
+  char msg[96] = "";
+  bool fma = false, cplx = false;
+  int threads = 0, nv = 0, tile = 0, ntiles = 0;
+  std::vector<CwtScalePlan> order;   // heaviest first
+  std::vector<CwtLaunch> launches;
+};
+void plan_cwt(const CwtCall& c, CwtPlan* p);
+
 // Banks with two lengths (Lhi != 0 and != L; the _bi_ entry points) run the same kernels on the PADDED ROUTE: the
 // shorter filter is zero-extended to args.taps = max(L, Lhi), or one tap further where only that count has
 // tap-unrolled kernels (VW_BI_LISTED, vw_plan.cpp listed_taps) -- for finite data a trailing 0 * x adds +-0 to a

@@ -409,6 +409,34 @@ class Engine:
                   wavelet_id, boundary, levels, self._flags(flags, dev), self._ptr(out, dev)))
         return out
 
+    # -- continuous wavelet transform (vw_cwt_*) ----------------------------------------------------
+    def cwt(self, x, scales, taps_re, taps_im, ext: int, wrap: int = 0, flags: int = 0, N: Optional[int] = None):
+        """out[b][s][tau] = (sum_k w_s[k] * ext(x_b, tau + o_s + k)) / q_s, k ascending.  x: [N] or [B, ld] (N: the
+        row length when the rows carry padding, ld > N).  scales: a sequence of (tap_begin, taps, window_begin,
+        divisor) into the flat float64 tables taps_re / taps_im (taps_im None: real output).  ext: nat.CWT_*; wrap:
+        the period of CWT_WRAP_ZERO.  -> (re, im or None), each [(B,) S, N]."""
+        xa, dev, xp, f32 = self._prep(x)
+        one = xa.ndim == 1
+        B, ld = (1, xa.shape[0]) if one else xa.shape
+        N = ld if N is None else int(N)
+        S = len(scales)
+        desc = (nat.CwtScale * max(S, 1))()
+        for i, (t0, k, o, q) in enumerate(scales):
+            desc[i] = nat.CwtScale(int(t0), int(k), int(o), float(q))
+        tre = np.ascontiguousarray(taps_re, dtype=np.float64)
+        tim = None if taps_im is None else np.ascontiguousarray(taps_im, dtype=np.float64)
+        if tim is not None and tim.shape != tre.shape:
+            raise ValueError("taps_im must have the shape of taps_re")
+        shape = (S, N) if one else (B, S, N)
+        ore = self._empty(xa, dev, shape)
+        oim = None if tim is None else self._empty(xa, dev, shape)
+        dpp = ctypes.POINTER(c_double)
+        fn = self.lib.vw_cwt_f32 if f32 else self.lib.vw_cwt_f64
+        _check(fn(self.ctx, xp, B, N, ld, desc, S, tre.ctypes.data_as(dpp),
+                  None if tim is None else tim.ctypes.data_as(dpp), tre.size, ext, wrap, self._flags(flags, dev),
+                  self._ptr(ore, dev), self._ptr(oim, dev)))
+        return ore, oim
+
     def transpose(self, a, rows: int, cols: int):
         """out[c][r] = a[r][c] (a: rows*cols elements, any shape) -> flat [cols*rows] array."""
         aa, dev, ap, f32 = self._prep(a)
