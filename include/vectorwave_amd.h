@@ -559,7 +559,8 @@ VW_API vw_status vw_graph_stats(vw_graph *graph, int *kernel_nodes, int *fused_p
  * kept): the same arrays, bit for bit, in both accumulation modes.  Where the pair is eligible -- device memory,
  * fp64, PERIODIC, a filter of at most 8 taps, rows the persistent forward takes whole (N a multiple of 512
  * samples up to 4096), no VALIDATE / REF_NONFINITE, y apart from x / details / approx -- one kernel runs both
- * halves per row, keeps a_J and d_J in registers and reads the other detail rows back right after storing them;
+ * halves per row, keeps a_J and d_J (and up to two more detail rows, below) in registers and reads the other detail
+ * rows back right after storing them;
  * otherwise the two kernels run.  lo / hi: the
  * analysis pair, rlo / rhi: the synthesis pair, L taps each.
  * While a context is capturing (vw_capture_begin), a vw_modwt_forward_f64 directly followed by its
@@ -571,6 +572,12 @@ VW_API vw_status vw_modwt_roundtrip_f64(vw_ctx *ctx, const double *x, int64_t B,
                                         double *approx, double *y);
 /* Resident workgroups per compute unit of that launch for rows of N samples (0: the shape is not eligible). */
 VW_API vw_status vw_roundtrip_occupancy(vw_ctx *ctx, int64_t N, int L, int J, unsigned flags, int *per_cu);
+/* The kernel keeps up to two more detail rows (d_{J-1}, d_{J-2}) in registers instead of reading them back: switch
+ * VW_PAIR_KEEP = 0 | 1 | 2 forces that many; unset or negative, the context takes the most that cost no resident
+ * workgroup.  Reports what a launch for rows of N samples on this context would run: *keep, the number of kept rows,
+ * and *per_cu as vw_roundtrip_occupancy does (both 0: the shape is not eligible).  The arrays are the same bit for
+ * bit whichever runs. */
+VW_API vw_status vw_roundtrip_variant(vw_ctx *ctx, int64_t N, int L, int J, unsigned flags, int *keep, int *per_cu);
 
 /* ---- pipelined round trips ---------------------------------------------------
  * A caller that runs forward + inverse over successive batches (a server's per-batch loop over

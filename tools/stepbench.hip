@@ -7,9 +7,12 @@
 // over R rotated buffer sets (R x 128 MiB of inputs >= 512 MiB, as bench.py --rotate), K steps timed
 // with HIP events, on 1 stream or with the rows split over S streams (bench.py's contexts schedule).
 //   ./stepbench [S]   -> JSON lines: pattern, ms per step, Msamples/s, GB/s (2.147 GB per step)
+//   ./stepbench roundtrip   -> the fused step's pattern (vw_pair.hip k_roundtrip) with r = 5, 4, 3, 0 planes read back:
+//                              what keeping 5 - r detail planes in registers (VW_PAIR_KEEP) can gain at the most
 #include <hip/hip_runtime.h>
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <vector>
 
 typedef double d2 __attribute__((ext_vector_type(2)));
@@ -61,6 +64,40 @@ __global__ void __launch_bounds__(512) fanin(const double* __restrict__ in, doub
   for (int k = 0; k < 4; ++k) __builtin_nontemporal_store(acc[k], reinterpret_cast<d2*>(y + b * N) + threadIdx.x + k * 512);
 }
 
+// The round-trip kernel's traffic with no arithmetic: a persistent workgroup (512 threads, 4 x 16 B per lane, the
+// product's LDS footprint so that two share a CU) walks rows b = row0 + blockIdx.x, + gridDim.x, ...  Per row it
+// loads x non-temporally, stores 7 planes sc1, waits until all but the last two planes' stores have retired
+// (vmcnt(8), the product's counted wait), reloads the r planes it stored first -- each lane its own vectors, the
+// most recently stored of them first, non-temporal buffer loads as plain_load_row's -- and stores y non-temporally.
+__global__ void __launch_bounds__(512) roundtrip(const double* __restrict__ x, double* out, double* __restrict__ y,
+                                                 int N, long long plane, long long rows, long long row0, int r) {
+  extern __shared__ double lds_hold[];
+  if (N < 0) lds_hold[threadIdx.x] = 0;
+  for (long long b = row0 + blockIdx.x; b < row0 + rows; b += gridDim.x) {
+    d2 v[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) v[k] = __builtin_nontemporal_load(reinterpret_cast<const d2*>(x + b * N) + threadIdx.x + k * 512);
+    for (int j = 0; j < 7; ++j) {
+#pragma unroll
+      for (int k = 0; k < 4; ++k)
+        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(i4, v[k] * (double)(j + 1)), rsrc(out + j * plane + b * N),
+                                               (threadIdx.x + k * 512) * 16, 0, 16);
+    }
+    d2 acc[4] = {v[0], v[1], v[2], v[3]};
+    if (r > 0) {
+      __builtin_amdgcn_s_waitcnt(0x0F78);  // vmcnt(8)
+      for (int j = r - 1; j >= 0; --j) {
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+          acc[k] += __builtin_bit_cast(d2, __builtin_amdgcn_raw_buffer_load_b128(rsrc(out + j * plane + b * N),
+                                                                                 (threadIdx.x + k * 512) * 16, 0, 2));
+      }
+    }
+#pragma unroll
+    for (int k = 0; k < 4; ++k) __builtin_nontemporal_store(acc[k], reinterpret_cast<d2*>(y + b * N) + threadIdx.x + k * 512);
+  }
+}
+
 int main(int argc, char** argv) {
   const int B = 4096, N = 4096, J = 7, R = 4, K = 20, WARM = 40;
   const long long plane = (long long)B * N;
@@ -90,6 +127,48 @@ int main(int argc, char** argv) {
   CHK(hipEventCreate(&e0));
   CHK(hipEventCreate(&e1));
   for (auto& e : done) CHK(hipEventCreate(&e));
+
+  if (argc > 1 && !strcmp(argv[1], "roundtrip")) {
+    // 1 stream x 4096 rows and 4 streams x 1024 rows, each launch a grid of min(rows, 2 x CUs) workgroups holding
+    // the product's 69,152 B of LDS (bench.py's contexts schedule; the product takes its grid the same way)
+    const int lds = 69152;
+    hipDeviceProp_t prop;
+    CHK(hipGetDeviceProperties(&prop, 0));
+    CHK(hipFuncSetAttribute((const void*)roundtrip, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+    for (int S : {1, 4}) {
+      for (int r : {5, 4, 3, 0}) {
+        const long long rows = B / S;
+        const unsigned grid = (unsigned)(rows < 2LL * prop.multiProcessorCount ? rows : 2LL * prop.multiProcessorCount);
+        auto issue = [&](int steps) {
+          for (int i = 0; i < steps; ++i)
+            for (int p = 0; p < S; ++p)
+              hipLaunchKernelGGL(roundtrip, dim3(grid), dim3(512), lds, st[p], sets[i % R].x, sets[i % R].c,
+                                 sets[i % R].y, N, pstr, rows, p * rows, r);
+        };
+        issue(WARM);
+        CHK(hipDeviceSynchronize());
+        for (int rep = 0; rep < 3; ++rep) {
+          CHK(hipEventRecord(e0, st[0]));
+          for (int p = 1; p < S; ++p) CHK(hipStreamWaitEvent(st[p], e0, 0));
+          issue(K);
+          for (int p = 1; p < S; ++p) {
+            CHK(hipEventRecord(done[p], st[p]));
+            CHK(hipStreamWaitEvent(st[0], done[p], 0));
+          }
+          CHK(hipEventRecord(e1, st[0]));
+          CHK(hipEventSynchronize(e1));
+          float ms = 0;
+          CHK(hipEventElapsedTime(&ms, e0, e1));
+          const double per = ms / K;
+          printf("{\"pattern\": \"round trip, 1 + 7 + 1 planes and %d read back\", \"streams\": %d, \"rep\": %d, "
+                 "\"ms_per_step\": %.4f, \"Msamples_per_s\": %.1f, \"GBps\": %.1f}\n", r, S, rep, per,
+                 plane / (per * 1e-3) / 1e6, plane * 8.0 * (9 + r) / (per * 1e-3) / 1e9);
+          fflush(stdout);
+        }
+      }
+    }
+    return 0;
+  }
 
   auto run = [&](const char* name, int S, auto fwd) {
     // S parts of B / S rows, part p on stream p; K steps, step i on set i mod R

@@ -146,6 +146,7 @@ SIGNATURES = {
     "vw_modwt_roundtrip_f64": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int64, _dp, _dp, _dp, _dp, c_int, c_int,
                                        c_int, c_int, c_uint, c_void_p, c_void_p, c_void_p]),
     "vw_roundtrip_occupancy": (c_int, [c_void_p, c_int64, c_int, c_int, c_uint, POINTER(c_int)]),
+    "vw_roundtrip_variant": (c_int, [c_void_p, c_int64, c_int, c_int, c_uint, POINTER(c_int), POINTER(c_int)]),
     # pipelined round trips: per-set arrays of device pointers (c_void_p * sets)
     "vw_pipeline_create": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int64,
                                    c_int64, _dp, _dp, c_int, c_int, c_int, c_int, c_uint, POINTER(c_void_p)]),

@@ -995,7 +995,7 @@ static void pair_after_forward(vw_ctx* c, const FwdCall<double>& k, const FwdPla
   c->pair.valid = false;
   if (!c->tune.pair_fuse || !pair_forward_shape(p)) return;
   if (!c->capturing) {
-    if (pair_prepare(a.taps, p.fma, p.threads, p.lds, nullptr) != hipSuccess) (void)hipGetLastError();
+    if (pair_prepare(a.taps, p.fma, p.threads, p.lds, c->tune.pair_keep, nullptr, nullptr) != hipSuccess) (void)hipGetLastError();
     return;
   }
   if (c->timing || p.ref_nf || p.validate) return;
@@ -1037,7 +1037,7 @@ static bool try_pair_fuse(vw_ctx* c, const InvCall<double>& k, const InvPlan<dou
   if (!pair_fusable(c->pair.call, c->pair.plan, k, p)) return false;
   const FwdPlan<double>& fp = c->pair.plan;
   PairLaunch l;
-  if (!pair_launch_shape(fp.args.taps, fp.fma, fp.threads, fp.lds, k.B, c->cus, &l)) return false;  // never run uncaptured
+  if (!pair_launch_shape(fp.args.taps, fp.fma, fp.threads, fp.lds, c->tune.pair_keep, k.B, c->cus, &l)) return false;  // never run uncaptured
   PairArgs<double> a;
   pair_args(c->pair.args, k, p, &a);
   void* params[] = {&a};
@@ -1454,8 +1454,9 @@ extern "C" vw_status vw_modwt_roundtrip_f64(vw_ctx* c, const double* x, int64_t 
       plan_inverse(c->tune, ik, &ip);
       PairLaunch l;
       if (pair_fusable(fk, fp, ik, ip) &&
-          (c->capturing || pair_prepare(fp.args.taps, fp.fma, fp.threads, fp.lds, nullptr) == hipSuccess) &&
-          pair_launch_shape(fp.args.taps, fp.fma, fp.threads, fp.lds, B, c->cus, &l)) {
+          (c->capturing ||
+           pair_prepare(fp.args.taps, fp.fma, fp.threads, fp.lds, c->tune.pair_keep, nullptr, nullptr) == hipSuccess) &&
+          pair_launch_shape(fp.args.taps, fp.fma, fp.threads, fp.lds, c->tune.pair_keep, B, c->cus, &l)) {
         FwdArgs<double> f = fp.args;
         f.x = x; f.details = details; f.approx = approx;
         f.bad = c->bad;
@@ -1478,9 +1479,10 @@ extern "C" vw_status vw_modwt_roundtrip_f64(vw_ctx* c, const double* x, int64_t 
   return modwt_inverse<double>(c, details, approx, B, N, rlo, rhi, L, wid, boundary, J, ~0u, 0, flags, y);
 }
 
-extern "C" vw_status vw_roundtrip_occupancy(vw_ctx* c, int64_t N, int L, int J, unsigned flags, int* per_cu) {
-  if (!c || !per_cu) return fail(VW_ERR_NULL, "null argument");
-  *per_cu = 0;
+// The round-trip launch for rows of N samples on this context: the variant VW_PAIR_KEEP and the occupancies choose
+// (kept detail planes) and its resident workgroups per CU; both 0 where the shape is not eligible.
+static vw_status roundtrip_variant(vw_ctx* c, int64_t N, int L, int J, unsigned flags, int* keep, int* per_cu) {
+  *keep = *per_cu = 0;
   if (N <= 0 || N > (1LL << 30) || L < 1 || L > kPairMaxTaps || J < 1 || J > kMaxLevels) return ok();
   std::lock_guard<std::recursive_mutex> g(c->mu);
   if (c->capturing) return fail(VW_ERR_STATE, "occupancy queries cannot be captured");
@@ -1495,11 +1497,22 @@ extern "C" vw_status vw_roundtrip_occupancy(vw_ctx* c, int64_t N, int L, int J, 
   FwdPlan<double> fp;
   plan_forward(c->tune, fk, &fp);
   if (fp.error != VW_OK || !pair_forward_shape(fp)) return ok();
-  if (pair_prepare(fp.args.taps, fp.fma, fp.threads, fp.lds, per_cu) != hipSuccess) {
+  if (pair_prepare(fp.args.taps, fp.fma, fp.threads, fp.lds, c->tune.pair_keep, per_cu, keep) != hipSuccess) {
     (void)hipGetLastError();
-    *per_cu = 0;
+    *keep = *per_cu = 0;
   }
   return ok();
+}
+
+extern "C" vw_status vw_roundtrip_occupancy(vw_ctx* c, int64_t N, int L, int J, unsigned flags, int* per_cu) {
+  if (!c || !per_cu) return fail(VW_ERR_NULL, "null argument");
+  int keep;
+  return roundtrip_variant(c, N, L, J, flags, &keep, per_cu);
+}
+
+extern "C" vw_status vw_roundtrip_variant(vw_ctx* c, int64_t N, int L, int J, unsigned flags, int* keep, int* per_cu) {
+  if (!c || !keep || !per_cu) return fail(VW_ERR_NULL, "null argument");
+  return roundtrip_variant(c, N, L, J, flags, keep, per_cu);
 }
 
 // Biorthogonal banks (BiorthogonalSpline / ReverseBiorthogonalSpline): lo has Llo taps, hi has Lhi.  Equal

@@ -865,7 +865,8 @@ __device__ __forceinline__ void nf_flag_row(int* flag, long long b, T z) {
 // registers besides being stored, in areg's layout (nullptr: nowhere).
 // INSTRUCTION COUNT: in the FULL form a lane issues exactly one vector-memory store per store_vec below, i.e. NV per
 // level and 2 * NV at the level that also writes aout, and nothing else.  The counted vmcnt waits of
-// k_forward_persist and k_roundtrip (vw_pair.hip: its reload of d_{J-1} behind the lane's own stores) depend on it.
+// k_forward_persist and k_roundtrip (vw_pair.hip: its first reload, of d_{J-1-KEEP}, behind the lane's own stores -- the
+// KEEP * NV stores of the kept planes' levels, then level J's 2 * NV, are all that follows that plane's) depend on it.
 template <typename T, int L, bool FMA, int NV, bool VALIDATE, bool NFP = false, bool FULL = false, int LH = L,
           int AUX = VW_FWD_STORE_AUX>
 __device__ __forceinline__ void fwd_level(const FwdArgs<T>& p, const T* X, int nvec, const LevelDesc& lv, T* dout,
@@ -998,7 +999,8 @@ __device__ __forceinline__ void lds_dma16(unsigned lds, const void* g, bool nt) 
 }
 
 // INSTRUCTION COUNT: under the full-slab contract (threads * NV == nvec, whole waves) a wave issues exactly NV of
-// these.  k_forward_persist's vmcnt(2 * NV) and k_roundtrip's vmcnt(3 * NV) / vmcnt(2 * NV) (vw_pair.hip) count on it.
+// these.  k_forward_persist's vmcnt(2 * NV) and k_roundtrip's vmcnt(3 * NV) / vmcnt(2 * NV) (vw_pair.hip: ahead of its
+// first reload, and closing the row where nothing is reloaded, J <= KEEP + 1) count on it.
 template <typename T>
 __device__ __forceinline__ void dma_row(T* buf, const T* __restrict__ src, int nvec, bool nt) {
   constexpr int V = VT<T>::V;

@@ -119,6 +119,13 @@ struct InvArgs {
 // share of an InvArgs (vw_plan.cpp pair_fusable: the spacings are the forward's, the level buffer is the
 // forward's region from its first element on).
 constexpr int kPairMaxTaps = 8;
+constexpr int kPairMaxKeep = 2;   // detail planes below d_J that k_roundtrip can keep in registers (VW_PAIR_KEEP)
+constexpr int kPairAutoKeep = 2;  // the most the auto rule takes: what measured best on the headline
+// Which k_roundtrip variant runs (vw_plan.cpp: host-only, no HIP call): the number of kept planes, 0 .. kPairMaxKeep.
+// requested (Tuning::pair_keep) >= 0 forces that variant, clamped to kPairMaxKeep.  Auto (< 0): the largest variant
+// <= kPairAutoKeep whose resident workgroups per CU (per_cu[v], from the occupancy query for the launch's threads and
+// LDS) are no fewer than variant 0's -- a kept plane is 16 VGPRs, and is never bought with a resident workgroup.
+int pair_keep_variant(int requested, const int (&per_cu)[kPairMaxKeep + 1]);
 template <typename T>
 struct PairArgs {
   FwdArgs<T> f;
@@ -436,13 +443,16 @@ hipError_t launch_inverse_fused(const InvArgs<T>& a, int threads, int lds_bytes,
 // resident workgroups per CU, may be null): neither can be recorded, so the executor calls it where an eligible
 // forward runs uncaptured.  pair_launch_shape gives the launch of a prepared (taps, mode, threads, lds) -- the
 // host function, the resident grid -- and false for one that is not prepared on the current device; it makes no
-// call a capture forbids.
+// call a capture forbids.  keep: Tuning::pair_keep, the requested number of kept detail planes (< 0: auto); both
+// prepare every variant and choose by pair_keep_variant (above), and report the choice (variant / keep) with its
+// resident workgroups per CU.
 struct PairLaunch {
   const void* func;
   unsigned grid, threads, lds;
+  int keep, per_cu;
 };
-hipError_t pair_prepare(int taps, bool fma, int threads, int lds_bytes, int* per_cu);
-bool pair_launch_shape(int taps, bool fma, int threads, int lds_bytes, long long B, int cus, PairLaunch* out);
+hipError_t pair_prepare(int taps, bool fma, int threads, int lds_bytes, int keep, int* per_cu, int* variant);
+bool pair_launch_shape(int taps, bool fma, int threads, int lds_bytes, int keep, long long B, int cus, PairLaunch* out);
 hipError_t launch_roundtrip(const PairArgs<double>& a, const PairLaunch& l, hipStream_t st);
 template <typename T>
 hipError_t launch_forward_level(const LevelArgs<T>& a, int lds_bytes, bool fma, hipStream_t st);

@@ -64,6 +64,7 @@ static const TuningKey kTuningTable[] = {
     VW_KEY("VW_BI_LISTED", t.bi_listed = v < 0 ? d.bi_listed : v != 0),
     VW_KEY("VW_INV_WAVES", t.inv_waves = v == 6 || v == 8 ? v : d.inv_waves),
     VW_KEY("VW_PAIR_FUSE", t.pair_fuse = v < 0 ? d.pair_fuse : v != 0),
+    VW_KEY("VW_PAIR_KEEP", t.pair_keep = v < 0 ? d.pair_keep : std::min(v, kPairMaxKeep)),
 };
 #undef VW_KEY
 
@@ -1264,6 +1265,13 @@ template bool pair_fusable<float>(const FwdCall<float>&, const FwdPlan<float>&, 
                                   const InvPlan<float>&);
 template bool pair_fusable<double>(const FwdCall<double>&, const FwdPlan<double>&, const InvCall<double>&,
                                    const InvPlan<double>&);
+
+int pair_keep_variant(int requested, const int (&per_cu)[kPairMaxKeep + 1]) {
+  if (requested >= 0) return std::min(requested, kPairMaxKeep);
+  int v = kPairAutoKeep;
+  while (v > 0 && per_cu[v] < per_cu[0]) --v;
+  return v;
+}
 
 template void plan_forward<float>(const Tuning&, const FwdCall<float>&, FwdPlan<float>*);
 template void plan_forward<double>(const Tuning&, const FwdCall<double>&, FwdPlan<double>*);

@@ -75,6 +75,8 @@ struct Tuning {
                                // 2: k_mra wherever it fits, also where it measured slower than the loop (plan_mra)
   int pair_fuse = 1;           // VW_PAIR_FUSE=0: a captured forward and the inverse that follows it stay two kernels;
                                // 1: one k_roundtrip launch where pair_fusable holds (vw_capi.cpp)
+  int pair_keep = -1;          // VW_PAIR_KEEP=0|1|2: k_roundtrip keeps that many detail planes below d_J in registers instead
+                               // of reading them back (larger values: 2); < 0: auto, see pair_keep_variant (vw_internal.h)
   int bi_listed = 1;           // VW_BI_LISTED=0: a two-length bank runs max(Llo, Lhi) taps even where that count is not in
                                // VW_TAP_LIST (the runtime-L kernels); 1: one more zero tap where that reaches a listed count
 };

@@ -250,6 +250,14 @@ class Engine:
         _check(self.lib.vw_roundtrip_occupancy(self.ctx, int(N), int(L), int(levels), int(flags), byref(n)))
         return n.value
 
+    def roundtrip_variant(self, N: int, L: int, levels: int, flags: int = 0):
+        """(kept detail planes, resident workgroups per CU) of the round-trip launch this context would make for
+        rows of N samples: the VW_PAIR_KEEP variant that runs ((0, 0): not eligible)."""
+        from ctypes import c_int
+        keep, n = c_int(), c_int()
+        _check(self.lib.vw_roundtrip_variant(self.ctx, int(N), int(L), int(levels), int(flags), byref(keep), byref(n)))
+        return keep.value, n.value
+
     def forward1(self, x, lo, hi, boundary: int, flags: int):
         xa, dev, xp, f32 = self._prep(x, np.float64)
         one = xa.ndim == 1
