@@ -61,6 +61,33 @@ def test_null_context_maps_to_npe():
         errors.raise_for_status(st, nat.last_error())
 
 
+def test_null_arguments_in_every_host_unit():
+    # The host layer is several translation units behind one thread-local error state: an entry point of each
+    # (vw_ctx.cpp, vw_api_modwt.cpp, vw_api_analysis.cpp, vw_api_denoise.cpp; vw_exec.cpp has none) reports a null
+    # context and a null array as before, and vw_last_error (vw_ctx.cpp) sees the message whichever unit raised it.
+    lib = nat.load()
+    lo = nat.taps_array([0.5, 0.5])
+    ctx = ctypes.create_string_buffer(8192)  # never read: the null-array checks come before any use of the context
+    x = np.zeros(8)
+    xp = ctypes.c_void_p(x.ctypes.data)
+    calls = [
+        (lambda c, a: lib.vw_fill_uniform_f64(c, a, 8, 42, 0), "null argument", "null argument"),
+        (lambda c, a: lib.vw_modwt_forward_f64(c, a, 1, 4, 4, lo, lo, 2, 0, 0, 1, 0, a, a),
+         "ctx is null", "null array argument"),
+        (lambda c, a: lib.vw_fin_sharpe_f64(c, a, 1, 4, 4, 0.0, 0, a), "ctx is null", "null array argument"),
+        (lambda c, a: lib.vw_noise_sigma_f64(c, a, 1, 4, 0, a), "null argument", "null argument"),
+    ]
+    for call, no_ctx, no_array in calls:
+        assert call(None, xp) == errors.VW_ERR_NULL
+        assert nat.last_error() == no_ctx
+        assert call(ctx, None) == errors.VW_ERR_NULL
+        assert nat.last_error() == no_array
+    # ... and a success in one unit clears what another raised
+    assert lib.vw_modwt_forward_f64(None, None, 1, 4, 4, lo, lo, 2, 0, 0, 1, 0, None, None) == errors.VW_ERR_NULL
+    assert lib.vw_window_gather_abs_f64(ctx, xp, None, 0, xp, 4, 0) == 0  # count == 0: nothing to do
+    assert nat.last_error() == ""
+
+
 def test_status_to_exception_mapping():
     with pytest.raises(errors.InvalidSignalException) as e:
         errors.raise_for_status(errors.VW_ERR_NONFINITE, "nan", 5)

@@ -4,6 +4,7 @@ bit-identical to direct calls; calls that must synchronize are refused while cap
 import numpy as np
 import pytest
 
+import host_calls as H
 from oracle import oracle as O
 import vectorwave_amd as vw
 from vectorwave_amd import _native as nat
@@ -66,6 +67,11 @@ def test_capture_refuses_synchronizing_calls(engine):
         engine.bind_torch_stream()
         lo, hi = nat.taps_array(w.lowPassDecomposition()), nat.taps_array(w.highPassDecomposition())
         lib, ctx = engine.lib, engine.ctx
+        engine.fill_uniform(x, 42)
+        assert lib.vw_modwt_forward_f64(ctx, c_void_p(x.data_ptr()), 4, 512, 512, lo, hi, len(lo), w.wavelet_id, 0, 3,
+                                        0, c_void_p(det.data_ptr()), c_void_p(app.data_ptr())) == 0
+        torch.cuda.synchronize()
+        d0, a0 = det.clone(), app.clone()
         assert lib.vw_capture_begin(ctx) == 0
         st = lib.vw_modwt_forward_f64(ctx, c_void_p(x.data_ptr()), 4, 512, 512, lo, hi, len(lo), w.wavelet_id, 0, 3,
                                       nat.FLAG_VALIDATE, c_void_p(det.data_ptr()), c_void_p(app.data_ptr()))
@@ -81,9 +87,25 @@ def test_capture_refuses_synchronizing_calls(engine):
                                                      nat.FLAG_HOST_MEMORY, c_void_p(xh.ctypes.data)))):
             assert fn(ctx, *args) == 10
             assert "captured" in nat.last_error()
+        # ... and so is every other entry point that takes VW_FLAG_HOST_MEMORY
+        sides = []
+        for name, call in H.CAPTURE_CALLS.items():
+            sides.append(H.Side())
+            assert call(lib, ctx, sides[-1], 2, 64, 2, nat.PERIODIC) == 10, name
+            assert "captured" in nat.last_error(), name
         assert lib.vw_capture_begin(ctx) == 10  # already capturing
+        # the capture is alive: it records a device-pointer forward, and its replay is that call's bits
+        assert lib.vw_modwt_forward_f64(ctx, c_void_p(x.data_ptr()), 4, 512, 512, lo, hi, len(lo), w.wavelet_id, 0, 3,
+                                        0, c_void_p(det.data_ptr()), c_void_p(app.data_ptr())) == 0
         g = c_void_p()
         assert lib.vw_capture_end(ctx, byref(g)) == 0
+        for side in sides:
+            side.close(lib)
+        for t in (det, app):
+            t.fill_(float("nan"))
+        assert lib.vw_graph_launch(g, 1) == 0
+        torch.cuda.synchronize()
+        assert torch.equal(det, d0) and torch.equal(app, a0)
         assert lib.vw_graph_destroy(g) == 0
     # the null stream cannot be captured
     engine.bind_torch_stream()

@@ -1,5 +1,5 @@
 // vw_internal.h -- shared between the HIP kernels (vw_kernels.hip), the planner (vw_plan.cpp) and the
-// C-ABI host layer (vw_capi.cpp).  Not installed; the public boundary is include/vectorwave_amd.h.
+// C-ABI host layer (vw_host.h: vw_ctx.cpp, vw_exec.cpp, vw_api_*.cpp).  Not installed; the public boundary is include/vectorwave_amd.h.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <atomic>
