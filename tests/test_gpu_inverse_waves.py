@@ -1,7 +1,7 @@
 """VW_INV_WAVES: the PLAIN form of the one-buffer inverse k_inverse_seq at 6 and at 8 waves per SIMD.
 
 A full-slab PERIODIC fp64 reconstruction of a short filter (L <= 8) from all of its coefficient planes runs
-inverse_seq_plain (vw_device.h), compiled for 6 waves per SIMD (three 512-thread workgroups per CU) and for 8
+inverse_seq_plain (vw_dev_inv.h), compiled for 6 waves per SIMD (three 512-thread workgroups per CU) and for 8
 (64 VGPRs: four).  Only registers, addresses and the number of LDS reads in flight differ between the two and
 from the general kernel: per output the taps, their order and the multiply/add instructions are the same, so y is
 bit-identical under both settings, EXACT is bit-exact against the restatement and FMA within 1e-12 of it

@@ -1,6 +1,6 @@
 """Compile-time level strides and full-slab forms of the fused short-filter kernels (VW_LEVEL_CT).
 
-With VW_LEVEL_CT=1 (vw_device.h fwd_row_ct / inv_row_ct) a strided level of a tap-unrolled filter (L <= 8) is
+With VW_LEVEL_CT=1 (vw_dev_rows.h fwd_row_ct / inv_row_ct) a strided level of a tap-unrolled filter (L <= 8) is
 dispatched once per row to a body with the spacing as a template constant (2..64; other spacings keep the
 run-time body), and k_forward_persist / k_inverse_seq run without per-vector bounds checks where the host
 contract makes every slab full.  Only addresses and control flow move: per output the taps, their order and

@@ -1,4 +1,4 @@
-"""Chained inverse column sweeps (vw_device.h k_inverse_sweep2 / k_inverse_sweep3): two or three deep
+"""Chained inverse column sweeps (vw_dev_lvl.h k_inverse_sweep2 / k_inverse_sweep3): two or three deep
 PERIODIC inverse levels in one launch, the intermediate approximations handed from one level's column
 sweep to the next through LDS rings (VW_SWEEP2 = 2: pairs only, 3: triples where they qualify).
 EXACT: bit-exact against the restatement of vectorwave-core (MultiLevelMODWTTransform.java:339-349,

@@ -84,7 +84,7 @@ def test_planner_marks_only_plain_calls(tmp_path):
     here = os.path.dirname(os.path.abspath(__file__))
     exe = os.path.join(str(tmp_path), "plan_waves")
     subprocess.run([os.environ.get("CXX", "g++"), "-O2", "-std=c++17", "-Wall", "-Wextra", "-Werror",
-                    "-D__HIP_PLATFORM_AMD__", "-I" + os.environ.get("HIP_INC", "/opt/rocm/include"), "-I" + CSRC,
+                    "-I" + CSRC,
                     "-o", exe, os.path.join(here, "plan_waves_harness", "plan_waves.cpp"),
                     os.path.join(CSRC, "vw_plan.cpp")], check=True, timeout=600)
     r = subprocess.run([exe], capture_output=True, text=True, timeout=60, check=True)

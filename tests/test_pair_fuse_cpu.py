@@ -29,7 +29,7 @@ NOT_FUSABLE = {"other_details", "other_approx", "masked_level", "approx_zero", "
 def test_planner_pairs_only_what_the_kernel_covers(tmp_path):
     exe = os.path.join(str(tmp_path), "pair_fuse")
     subprocess.run([os.environ.get("CXX", "g++"), "-O2", "-std=c++17", "-Wall", "-Wextra", "-Werror",
-                    "-D__HIP_PLATFORM_AMD__", "-I" + os.environ.get("HIP_INC", "/opt/rocm/include"), "-I" + CSRC,
+                    "-I" + CSRC,
                     "-o", exe, os.path.join(HERE, "pair_fuse_harness", "pair_fuse.cpp"),
                     os.path.join(CSRC, "vw_plan.cpp")], check=True, timeout=600)
     r = subprocess.run([exe], capture_output=True, text=True, timeout=60, check=True)
@@ -87,8 +87,8 @@ def test_headline_lds_lets_two_workgroups_share_a_cu(tmp_path):
                 '(uintptr_t(4) << 30);\nc.B = 4096; c.N = 4096; c.ldx = 4096; c.L = 8; c.J = 6; c.flags = VW_FLAG_FMA;\n'
                 'FwdPlan<double> p; plan_forward(Tuning(), c, &p); printf("%d %d\\n", p.kernel == kFwdPersist, p.lds);'
                 ' return 0; }\n')
-    subprocess.run([os.environ.get("CXX", "g++"), "-O2", "-std=c++17", "-D__HIP_PLATFORM_AMD__",
-                    "-I" + os.environ.get("HIP_INC", "/opt/rocm/include"), "-I" + CSRC, "-o", exe, src,
+    subprocess.run([os.environ.get("CXX", "g++"), "-O2", "-std=c++17",
+                    "-I" + CSRC, "-o", exe, src,
                     os.path.join(CSRC, "vw_plan.cpp")], check=True, timeout=600)
     persist, lds = (int(v) for v in subprocess.run([exe], capture_output=True, text=True, check=True).stdout.split())
     print("headline LDS bytes:", lds)

@@ -7,7 +7,7 @@ NAME=$1; EXTRA=$2; TAPS=${3:-X(8)}
 D="$ROOT/${VARDIR:-build}/var_$NAME"
 mkdir -p "$D/src/csrc" "$D/include"
 cp "$ROOT"/vectorwave_amd/csrc/* "$D/src/csrc/" 2>/dev/null || true
-rm -f "$D"/src/csrc/*.o
+rm -f "$D"/src/csrc/*.o "$D"/src/csrc/*.d
 cp "$ROOT"/include/*.h "$D/include/"
 # the Makefile's include path is ../../include relative to csrc
 mkdir -p "$D/src/include" && cp "$ROOT"/include/*.h "$D/src/include/"

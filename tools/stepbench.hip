@@ -1,7 +1,7 @@
 // stepbench.hip -- ceiling of the headline step's exact HBM pattern (calibration, not product).
 //
 // The db4 J=6 4096 x 4096 fp64 step (bench.py): the forward reads x (1 plane) and writes
-// d_1..d_6, a_6 (7 planes) with the sc1 store policy (vw_device.h VW_FWD_STORE_AUX = 16); the inverse
+// d_1..d_6, a_6 (7 planes) with the sc1 store policy (vw_dev_core.h VW_FWD_STORE_AUX = 16); the inverse
 // reads those 7 planes non-temporally and writes y (1 plane) non-temporally.  Here the same bytes move
 // with no arithmetic: one 512-thread workgroup per 4096-sample row, 4 x 16-byte vectors per thread,
 // over R rotated buffer sets (R x 128 MiB of inputs >= 512 MiB, as bench.py --rotate), K steps timed

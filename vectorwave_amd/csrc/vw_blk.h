@@ -1,7 +1,8 @@
 #pragma once
 // vw_blk.h -- the register-blocked PERIODIC kernels for long filters (k_forward_blk / k_inverse_blk) and
-// their shared pieces.  Included by vw_device.h, after the helpers it uses (VT, vmadd, static_for,
-// lds_base, the row transfers) and before the per-level kernels, whose k_inverse_multi borrows BlkC.
+// their shared pieces, on vw_dev_core.h's helpers (VT, vmadd, static_for, lds_base, the row transfers) and, for the
+// levels with s < V, vw_dev_rows.h's row bodies.  Included by the units that launch the two kernels and by
+// vw_dev_lvl.h, whose k_inverse_multi borrows BlkC.
 //
 // Three things are stated once here:
 //   * the padded layout rule is blk_pad (vw_internal.h, shared with the planner); BlkC is its
@@ -9,6 +10,9 @@
 //   * the tap loops are blk_inv_taps / blk_fwd_taps; the ways of reading LDS (per lane, compile-time
 //     offsets, wave-uniform offsets, immediates off a laundered base) are readers passed to them;
 //   * the dispatch on a compile-time vector stride is blk_stride.
+#include "vw_dev_rows.h"
+
+#pragma clang fp contract(off)
 
 namespace vw {
 

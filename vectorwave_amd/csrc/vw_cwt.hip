@@ -14,7 +14,7 @@
 // the staged tile: one chunk read (two 16-byte LDS reads) per NV taps feeds NV * NV multiplies, 2 NV * NV with a
 // complex table.  The taps are wave-uniform and read through scalar loads.  Each output keeps its own k order,
 // so without FMA the sums are the reference's bit for bit.
-#include "vw_internal.h"
+#include "vw_launch_k.h"
 
 #ifndef VW_T
 #error "compile with -DVW_T=double or -DVW_T=float"
@@ -143,12 +143,7 @@ __global__ void __launch_bounds__(kCwtThreads)
 
 template <typename T, bool CPLX, bool FMA>
 static hipError_t run_cwt(const CwtArgs<T>& a, int threads, int lds, int grid, hipStream_t st) {
-  auto k = k_cwt<T, CPLX, FMA>;
-  static LdsOnce configured;
-  hipError_t e = set_lds(k, lds, &configured);
-  if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(k, dim3((unsigned)grid), dim3(threads), lds, st, a, a.sc, a.taps_re, a.taps_im);
-  return hipGetLastError();
+  return launch_k<k_cwt<T, CPLX, FMA>>(dim3((unsigned)grid), dim3(threads), lds, st, a, a.sc, a.taps_re, a.taps_im);
 }
 
 template <typename T>

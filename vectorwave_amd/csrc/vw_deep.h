@@ -31,7 +31,4 @@ struct DeepArgs {
   T hi[kMaxTaps];
 };
 
-template <typename T>
-hipError_t launch_deep(const DeepArgs<T>& a, int lds_bytes, bool fma, bool inverse, hipStream_t st);
-
 }  // namespace vw

@@ -22,8 +22,8 @@
 // the not-yet-valid start of a ring are never stored (the reach argument), so uninitialised LDS is
 // harmless.  Per output the taps run in the reference's order (forward: i ascending, both filters
 // from one read; inverse: approximation branch then detail branch) -> bit-exact in EXACT mode.
-#include "vw_launch.h"
-#include "vw_deep.h"
+#include "vw_launch_k.h"
+#include "vw_dev_core.h"
 #include <algorithm>
 
 namespace vw {
@@ -458,29 +458,14 @@ __global__ void __launch_bounds__(kDeepThreads) k_inverse_deep(const DeepArgs<T>
   }
 }
 
-template <typename T, int L, bool FMA, bool INV>
-static hipError_t run_deep(const DeepArgs<T>& a, int lds, hipStream_t st) {
-  auto k = INV ? k_inverse_deep<T, L, FMA> : k_forward_deep<T, L, FMA>;
-  static LdsOnce configured;
-  hipError_t e = set_lds(k, lds, &configured);
-  if (e != hipSuccess) return e;
-  const long long groups = (a.B * a.seg + 7) / 8 * 8;
-  hipLaunchKernelGGL(k, dim3((unsigned)(groups * a.nb)), dim3(kDeepThreads), lds, st, a);
-  return hipGetLastError();
-}
-
 template <typename T>
 hipError_t launch_deep(const DeepArgs<T>& a, int lds_bytes, bool fma, bool inverse, hipStream_t st) {
-  switch (a.taps) {
-#define VW_CASE(n)                                                                                    \
-    case n:                                                                                           \
-      if (inverse) return fma ? run_deep<T, n, true, true>(a, lds_bytes, st) : run_deep<T, n, false, true>(a, lds_bytes, st); \
-      return fma ? run_deep<T, n, true, false>(a, lds_bytes, st) : run_deep<T, n, false, false>(a, lds_bytes, st);
-    VW_TAP_LIST(VW_CASE)
-#undef VW_CASE
-    default:
-      return hipErrorNotSupported;
-  }
+  const long long groups = (a.B * a.seg + 7) / 8 * 8;
+  const dim3 grid((unsigned)(groups * a.nb)), block(kDeepThreads);
+  return dispatch_taps<Unlisted::kNotSupported>(a.taps, fma, [&](auto l, auto m) {
+    if (inverse) return launch_k<k_inverse_deep<T, l(), m()>>(grid, block, lds_bytes, st, a);
+    return launch_k<k_forward_deep<T, l(), m()>>(grid, block, lds_bytes, st, a);
+  });
 }
 template hipError_t launch_deep<VW_T>(const DeepArgs<VW_T>&, int, bool, bool, hipStream_t);
 

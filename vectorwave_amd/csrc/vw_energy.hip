@@ -17,7 +17,8 @@
 //  * k_energy_rows_tree: planes in memory, VW_FLAG_TREE_SUMS: one workgroup per row, per-thread partials
 //    and the fixed-order workgroup sum.
 // Built with -ffp-contract=off: a square is rounded, then added.
-#include "vw_device.h"
+#include "vw_launch_k.h"
+#include "vw_dev_rows.h"
 
 #include <algorithm>
 
@@ -125,41 +126,17 @@ __global__ void VW_FUSED_BOUNDS(NV, VW_FUSED_W(L, 6)) k_energy_fused(const Energ
   }
 }
 
-template <int L, bool FMA, int NV>
-static hipError_t run_energy_fused(const EnergyArgs& a, int threads, int lds, int grid, hipStream_t st) {
-  auto k = k_energy_fused<L, FMA, NV>;
-  static LdsOnce configured;
-  hipError_t e = set_lds(k, lds, &configured);
-  if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(k, dim3((unsigned)grid), dim3(threads), lds, st, a);
-  return hipGetLastError();
-}
-
-template <int L, bool FMA>
-static hipError_t run_energy_fused_nv(const EnergyArgs& a, int threads, int lds, int nv, int grid, hipStream_t st) {
-  return nv <= 4 ? run_energy_fused<L, FMA, 4>(a, threads, lds, grid, st)
-                 : run_energy_fused<L, FMA, 8>(a, threads, lds, grid, st);
-}
-
 hipError_t launch_energy_fused(const EnergyArgs& a, int threads, int lds, bool fma, int nv, int grid, hipStream_t st) {
   if (threads <= 0 || threads % 64 != 0 || grid <= 0 || (nv != 4 && nv != 8)) return hipErrorInvalidConfiguration;
+  auto run = [&](auto l, auto m) {
+    if (nv <= 4) return launch_k<k_energy_fused<l(), m(), 4>>(dim3((unsigned)grid), dim3(threads), lds, st, a);
+    return launch_k<k_energy_fused<l(), m(), 8>>(dim3((unsigned)grid), dim3(threads), lds, st, a);
+  };
   // Tap-unrolled bodies for the short filters only (kEnergyUnrollMax): under this kernel's register budget the
-  // longer filters' unrolled windows spill to scratch, so they -- like unaligned rows, partial slabs and unlisted
-  // lengths -- take the runtime-L body, which does not.
-  switch (a.unrolled ? a.taps : 0) {
-#define VW_CASE(n)                                                                             \
-    case n:                                                                                    \
-      if constexpr (n <= kEnergyUnrollMax)                                                     \
-        return fma ? run_energy_fused_nv<n, true>(a, threads, lds, nv, grid, st)               \
-                   : run_energy_fused_nv<n, false>(a, threads, lds, nv, grid, st);             \
-      break;
-    VW_TAP_LIST(VW_CASE)
-#undef VW_CASE
-    default: break;
-  }
-  if (a.unrolled) return hipErrorInvalidConfiguration;  // plan_energy names no kernel this unit lacks
-  return fma ? run_energy_fused_nv<0, true>(a, threads, lds, nv, grid, st)
-             : run_energy_fused_nv<0, false>(a, threads, lds, nv, grid, st);
+  // longer filters' unrolled windows spill to scratch, so they -- like unaligned rows and partial slabs -- take the
+  // runtime-L body, which does not (plan_energy names no kernel this unit lacks).
+  if (a.unrolled) return dispatch_taps<Unlisted::kInvalidConfiguration, kEnergyUnrollMax>(a.taps, fma, run);
+  return with_fma(fma, [&](auto m) { return run(std::integral_constant<int, 0>{}, m); });
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -259,13 +236,12 @@ hipError_t launch_energy_planes(const EnergyPlanesArgs& a, bool tree, int cus, h
   if (tree) {
     const long long rows = ((long long)a.J + 1) * a.B;
     const long long grid = std::min<long long>(rows, 8LL * std::max(cus, 1));
-    hipLaunchKernelGGL(k_energy_rows_tree, dim3((unsigned)grid), dim3(256), 0, st, a);
+    return launch_k<k_energy_rows_tree>(dim3((unsigned)grid), dim3(256), 0, st, a);
   } else {
     const long long grid = (a.B + 63) / 64 + ((long long)a.J * a.B + 63) / 64;
     if (grid > 0x7fffffffLL) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(k_energy_chain, dim3((unsigned)grid), dim3(64), 0, st, a);
+    return launch_k<k_energy_chain>(dim3((unsigned)grid), dim3(64), 0, st, a);
   }
-  return hipGetLastError();
 }
 
 }  // namespace vw

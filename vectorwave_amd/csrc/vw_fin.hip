@@ -12,7 +12,7 @@
 // (bit-identical; the dependent fp64 adds of that walk, not HBM, bound the kernel).  With
 // FinArgs::tree every sum is per-thread partials + a wave / workgroup tree (VW_FLAG_TREE_SUMS).
 // Maxima and `any` do not depend on the order and are always reduced in parallel.
-#include "vw_internal.h"
+#include "vw_launch_k.h"
 
 namespace vw {
 
@@ -334,22 +334,14 @@ static int fin_lds(int n) { return (((n + 1) & ~1) + kFinScratch) * (int)sizeof(
 
 hipError_t launch_fin_analyze(const FinArgs& a, hipStream_t st) {
   const int n = a.N - 1, lds = fin_lds(n);
-  static LdsOnce configured;
-  hipError_t e = set_lds(k_fin_analyze, lds, &configured);
-  if (e != hipSuccess) return e;
   const unsigned grid = (unsigned)(a.B < (1LL << 20) ? a.B : (1LL << 20));
-  hipLaunchKernelGGL(k_fin_analyze, dim3(grid), dim3(fin_threads(n)), lds, st, a);
-  return hipGetLastError();
+  return launch_k<k_fin_analyze>(dim3(grid), dim3(fin_threads(n)), lds, st, a);
 }
 
 hipError_t launch_fin_sharpe(const FinArgs& a, hipStream_t st) {
   const int lds = fin_lds(a.N);
-  static LdsOnce configured;
-  hipError_t e = set_lds(k_fin_sharpe, lds, &configured);
-  if (e != hipSuccess) return e;
   const unsigned grid = (unsigned)(a.B < (1LL << 20) ? a.B : (1LL << 20));
-  hipLaunchKernelGGL(k_fin_sharpe, dim3(grid), dim3(fin_threads(a.N)), lds, st, a);
-  return hipGetLastError();
+  return launch_k<k_fin_sharpe>(dim3(grid), dim3(fin_threads(a.N)), lds, st, a);
 }
 
 }  // namespace vw

@@ -4,8 +4,7 @@
 // its FwdCall / InvCall once, opens a Staging, runs the device function and returns finish() ("Where kernel selection lives").
 #pragma once
 #include "../../include/vectorwave_amd.h"
-#include "vw_internal.h"
-#include "vw_deep.h"
+#include "vw_launch.h"
 #include "vw_plan.h"
 
 #include <algorithm>

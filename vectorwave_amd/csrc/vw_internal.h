@@ -1,8 +1,9 @@
-// vw_internal.h -- shared between the HIP kernels (vw_kernels.hip), the planner (vw_plan.cpp) and the
-// C-ABI host layer (vw_host.h: vw_ctx.cpp, vw_exec.cpp, vw_api_*.cpp).  Not installed; the public boundary is include/vectorwave_amd.h.
+// vw_internal.h -- what the HIP kernels (vw_dev_*.h, *.hip), the planner (vw_plan.cpp) and the C-ABI host layer
+// (vw_host.h: vw_ctx.cpp, vw_exec.cpp, vw_api_*.cpp) share: constants, the kernels' argument structs and the layout
+// rules both sides apply.  Plain C++: no HIP header, no launcher (those are declared in vw_launch.h).  Not installed;
+// the public boundary is include/vectorwave_amd.h.
 #pragma once
-#include <hip/hip_runtime.h>
-#include <atomic>
+#include <cstddef>
 #include <cstdint>
 #include "vw_taps.h"
 
@@ -13,7 +14,7 @@ constexpr int kMaxLevels = 24;  // batch semantics have no level cap; LDS / N bo
 constexpr int kNV = 8;          // max vectors (16 B each) held per thread in the fused kernels (NV = 4 or 8)
 constexpr int kMaxThreads = 1024;
 constexpr int kLdsBytes = 160 * 1024;
-constexpr int kSweepMinS = 16;    // per-level path: spacings >= this run as column sweeps (vw_device.h)
+constexpr int kSweepMinS = 16;    // per-level path: spacings >= this run as column sweeps (vw_dev_lvl.h)
 constexpr int kSweepChunk = 128;  // q-chunk per sweep thread (measured: 128 beats 256 and 64)
 
 // Source of the values outside [0, N) of a level's input ("halo"), i.e. the reference's index map.
@@ -36,7 +37,7 @@ struct LevelDesc {
   int off_d;
   int use_d;    // inverse: 1 = d_j from memory, 0 = zero details (reconstructFromLevel / Levels)
   int hist_len; // streaming: left history length of this level (L_j - 1)
-  int own;      // 1: halo written by the element owners (vw_device.h halo_images), else filled after a barrier
+  int own;      // 1: halo written by the element owners (vw_dev_core.h halo_images), else filled after a barrier
   int il_a, il_b;  // left image of element t: il_a*t + il_b (kept when in [-hl, 0))
   int ir_a, ir_b;  // right image: ir_a*t + ir_b (kept when in [N, N+hr))
   int vs, ve;   // only vectors w < vs or w >= ve have images
@@ -58,7 +59,7 @@ struct FwdArgs {
   int unrolled;         // 1: the tap-unrolled kernel may run (aligned rows, full slabs; vw_plan.cpp fused_plan)
   int dma_nt;           // k_forward_persist: non-temporal LDS-DMA of the signal rows
   int level_ct;         // 1: strided levels of short filters dispatch to compile-time-stride bodies, and
-                        // k_forward_persist runs its full-slab form (VW_LEVEL_CT; vw_device.h fwd_row_ct)
+                        // k_forward_persist runs its full-slab form (VW_LEVEL_CT; vw_dev_rows.h fwd_row_ct)
   int validate;         // 1: non-finite check on input and outputs (atomicMin into *bad)
   int rev;              // 1: workgroup g owns signal B-1-g (walk order: VW_FWD_REV, vw_plan.h Tuning)
   unsigned long long* bad;
@@ -90,7 +91,7 @@ struct InvArgs {
   int vec_io;
   int pair;             // 1: sum += (h*a + g*d) per tap (MODWTTransform.inverse, ZERO multi-level)
   int unrolled;
-  int level_ct;         // 1: compile-time-stride level bodies (VW_LEVEL_CT; vw_device.h inv_row_ct)
+  int level_ct;         // 1: compile-time-stride level bodies (VW_LEVEL_CT; vw_dev_rows.h inv_row_ct)
   int full;             // 1: aligned rows, threads * NV == N / V: k_inverse_seq's full-slab form may run
   int plain;            // 1 (with full, fp64): PERIODIC from every coefficient plane -- all levels read t + i*s with
                         // hr <= N, no threshold, no zeroed plane, no probe, forward walk: k_inverse_seq's PLAIN form
@@ -171,7 +172,7 @@ struct LevelArgs {
 };
 
 // Multi-level tiles (PERIODIC, long signals): a group of consecutive levels of one tile in one
-// launch, the intermediate approximations kept in LDS (vw_device.h k_forward_multi / k_inverse_multi).
+// launch, the intermediate approximations kept in LDS (vw_dev_lvl.h k_forward_multi / k_inverse_multi).
 constexpr int kMaxGroup = 8;
 constexpr int kMultiInvNI = 8;  // k_inverse_multi: output vectors per thread (256 threads)
 constexpr int kMultiPF = 6;     // k_inverse_multi: prefetched detail vectors per thread (256 threads)
@@ -262,15 +263,7 @@ struct RefArgs {
   T hi[kMaxTaps];
   LevelDesc lv[kMaxLevels];     // inverse: use_d, K6 orientation / offsets
 };
-template <typename T>
-hipError_t launch_flag_nonfinite(const RefScan<T>& a, hipStream_t st);
-template <typename T>
-hipError_t launch_ref_cascade(const RefArgs<T>& a, int grid, bool inverse, hipStream_t st);
 int ref_scan_chunks(int N);
-
-// Matrix-core fp32 kernels (vw_mfma.hip); mfma_supported / mfma_halo / mfma_region: vw_taps.h
-hipError_t launch_forward_mfma(const FwdArgs<float>& a, int lds, hipStream_t st);
-hipError_t launch_inverse_mfma(const InvArgs<float>& a, int lds, hipStream_t st);
 
 // Financial analytics (vw_fin.hip): one workgroup per row, the row's level-1 coefficients in LDS.
 constexpr int kFinMaxN = 16384;    // longest row (returns for analyze, N for the Sharpe calls): 8 * n bytes of LDS
@@ -291,8 +284,6 @@ struct FinArgs {
   double lo[kFinMaxTaps];  // base taps * 1/sqrt(2), as the transform kernels
   double hi[kFinMaxTaps];
 };
-hipError_t launch_fin_analyze(const FinArgs& a, hipStream_t st);
-hipError_t launch_fin_sharpe(const FinArgs& a, hipStream_t st);
 
 // Wavelet energy per level (vw_energy.hip): out[0][b] = sum a_J[b][t]^2, out[j][b] = sum d_j[b][t]^2, fp64.
 constexpr int kEnergyWaves = kMaxThreads / 64;
@@ -329,10 +320,6 @@ struct EnergyPlanesArgs {
   int vec_io;           // 1: N even and both arrays 16-byte aligned (every row then is)
   double* out;          // [J+1][B]
 };
-hipError_t launch_energy_fused(const EnergyArgs& a, int threads, int lds_bytes, bool fma, int nv, int grid,
-                               hipStream_t st);
-// tree = false: the reference's sequential sum per row (one lane per row); true: a workgroup tree per row
-hipError_t launch_energy_planes(const EnergyPlanesArgs& a, bool tree, int cus, hipStream_t st);
 
 // Multiresolution analysis (vw_mra.hip k_mra): out[0] = the smooth (a_J alone), out[c] = detail component c (d_c
 // alone), each the masked inverse with the branch passes over zeroed planes left out.
@@ -356,8 +343,6 @@ struct MraArgs {
   T hi[kMaxTaps];
   LevelDesc lv[kMaxLevels];  // inverse_levels' descriptors: dir_a / off_a / dir_d / off_d per branch
 };
-template <typename T>
-hipError_t launch_mra(const MraArgs<T>& a, int threads, int lds_bytes, bool fma, int nv, int grid, hipStream_t st);
 
 // Continuous wavelet transform (vw_cwt.hip k_cwt): out[b][s][tau] = (sum_k w_s[k] * ext(x_b, tau + o_s + k)) / q_s,
 // k ascending from an accumulator at +0.0 -- CWTTransform.analyzeDirect / analyzeDirectComplex (:120-218) with the
@@ -404,98 +389,6 @@ struct CwtArgs {
   int ext;                     // CwtExt
   long long wrap;              // M of kCwtWrapZero
 };
-template <typename T>
-hipError_t launch_cwt(const CwtArgs<T>& a, int threads, int lds_bytes, bool cplx, bool fma, int grid, hipStream_t st);
-
-// Raise a kernel's dynamic-LDS limit past the 64 KiB default once per kernel instantiation AND
-// device (the attribute belongs to the device's copy of the function; a call per launch costs host
-// time).  `once` is a static of the caller, unique per kernel instantiation; several host threads
-// (one per context, vw_modwt_*_multi_f64) may race here -- the attribute call is idempotent and the
-// flag is atomic.
-constexpr int kMaxDevices = 64;
-struct LdsOnce {
-  std::atomic<int> limit[kMaxDevices];  // zero-initialised as a static: the 64 KiB default applies
-};
-template <typename Kern>
-static hipError_t set_lds(Kern k, int lds_bytes, LdsOnce* once, int want = kLdsBytes) {
-  if (lds_bytes <= 64 * 1024) return hipSuccess;
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0) dev = 0;
-  std::atomic<int>* f = dev < kMaxDevices ? &once->limit[dev] : nullptr;
-  if (f && f->load(std::memory_order_acquire) >= lds_bytes) return hipSuccess;
-  if (want < lds_bytes) want = lds_bytes;
-  hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, want);
-  if (e != hipSuccess) return e;
-  if (f) f->store(want, std::memory_order_release);
-  return hipSuccess;
-}
-
-// Launchers (vw_kernels.hip).  Return hipSuccess or the launch error.
-template <typename T>
-hipError_t launch_forward_fused(const FwdArgs<T>& a, int threads, int lds_bytes, bool fma, int nv, hipStream_t st);
-template <typename T>
-hipError_t launch_forward_persist(const FwdArgs<T>& a, int threads, int lds_bytes, bool fma, int nv, hipStream_t st);
-template <typename T>
-hipError_t launch_forward_blk(const FwdArgs<T>& a, int threads, int lds_bytes, bool fma, int nv, hipStream_t st);
-template <typename T>
-hipError_t launch_inverse_fused(const InvArgs<T>& a, int threads, int lds_bytes, bool fma, int nv, hipStream_t st);
-// k_roundtrip (vw_pair.hip).  pair_prepare raises the kernel's dynamic-LDS limit and queries its occupancy (per_cu:
-// resident workgroups per CU, may be null): neither can be recorded, so the executor calls it where an eligible
-// forward runs uncaptured.  pair_launch_shape gives the launch of a prepared (taps, mode, threads, lds) -- the
-// host function, the resident grid -- and false for one that is not prepared on the current device; it makes no
-// call a capture forbids.  keep: Tuning::pair_keep, the requested number of kept detail planes (< 0: auto); both
-// prepare every variant and choose by pair_keep_variant (above), and report the choice (variant / keep) with its
-// resident workgroups per CU.
-struct PairLaunch {
-  const void* func;
-  unsigned grid, threads, lds;
-  int keep, per_cu;
-};
-hipError_t pair_prepare(int taps, bool fma, int threads, int lds_bytes, int keep, int* per_cu, int* variant);
-bool pair_launch_shape(int taps, bool fma, int threads, int lds_bytes, int keep, long long B, int cus, PairLaunch* out);
-hipError_t launch_roundtrip(const PairArgs<double>& a, const PairLaunch& l, hipStream_t st);
-template <typename T>
-hipError_t launch_forward_level(const LevelArgs<T>& a, int lds_bytes, bool fma, hipStream_t st);
-template <typename T>
-hipError_t launch_inverse_level(const LevelArgs<T>& a, int lds_bytes, bool fma, hipStream_t st);
-template <typename T>
-hipError_t launch_forward_sweep(const LevelArgs<T>& a, bool fma, hipStream_t st);
-template <typename T>
-hipError_t launch_inverse_sweep(const LevelArgs<T>& a, bool fma, hipStream_t st);
-template <typename T>
-hipError_t launch_inverse_sweepg(const LevelArgs<T>& a, int levels, int ka, int R, bool fma, hipStream_t st);
-template <typename T>
-hipError_t launch_forward_multi(const MultiArgs<T>& a, int lds_bytes, bool fma, hipStream_t st);
-
-template <typename T>
-hipError_t launch_inverse_multi(const MultiArgs<T>& a, int lds_bytes, bool fma, hipStream_t st);
-template <typename T>
-hipError_t launch_history_update(const T* level_in, long long ld_in, const T* old_hist, T* new_hist,
-                                 long long B, int n, int hist_len, hipStream_t st);
-
-hipError_t launch_level_threshold(const double* coeffs, long long level_stride, const double* sigma,
-                                  const DenoiseConsts& k, long long B, int levels, double* thr, hipStream_t st);
-hipError_t launch_noise_sigma(const double* coeffs, long long ld, long long B, int N, double scale_c,
-                              double* sigma_out, double* thr_out, hipStream_t st);
-// Exact median of |x - center| per row (center nullptr: of |x|); N <= 16384 when center is given.
-hipError_t launch_median(const double* x, long long ld, long long B, int N, const double* center, double* median_out,
-                         hipStream_t st);
-// out[b][i] = |x[b*ld + i] - center[b]| (MathUtils.medianAbsoluteDeviation's deviations), for the
-// centered median of rows longer than the register-keyed path holds.
-hipError_t launch_abs_center(const double* x, long long ld, long long B, int N, const double* center, double* out,
-                             hipStream_t st);
-hipError_t launch_seq_std(const double* x, int n, double* out, hipStream_t st);
-hipError_t launch_gather_abs(const double* src, const int* idx, int count, double* window, int wsize, int start,
-                             hipStream_t st);
-template <typename T>
-hipError_t launch_transpose(const T* in, long long rows, long long cols, T* out, hipStream_t st);
-template <typename T>
-hipError_t launch_threshold(T* c, long long B, long long N, const T* thr, int soft, hipStream_t st);
-template <typename T>
-hipError_t launch_fill_uniform(T* x, long long count, unsigned long long seed, long long offset, hipStream_t st);
-template <typename T>
-hipError_t launch_single_haar_batch(const T* x, long long ldx, long long B, int N, T* approx, T* detail,
-                                    hipStream_t st);
 
 // Register-blocked kernels (vw_blk.h k_forward_blk / k_inverse_blk, and k_inverse_multi's blocked levels):
 // the padded LDS layout of a level with vector stride m and nv outputs per thread, the one rule for the
@@ -513,7 +406,5 @@ constexpr BlkLayout blk_pad(int m, int nv, int tight = 0) {
   if (m == 8) return BlkLayout{3, 2};
   return BlkLayout{2, 1};
 }
-
-int fused_max_threads();
 
 }  // namespace vw

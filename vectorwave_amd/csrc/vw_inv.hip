@@ -1,39 +1,53 @@
-// vw_inv.hip -- launchers (instantiation unit, once per element type) for the kernels in vw_device.h.
-#include "vw_launch.h"
-#include <algorithm>
+// vw_inv.hip -- launchers (instantiation unit, once per element type: -DVW_T=double / float) of the fused inverse
+// kernels (vw_dev_inv.h) and the register-blocked inverse (vw_blk.h).
+#include "vw_launch_k.h"
+#include "vw_dev_inv.h"
+#include "vw_blk.h"
 
 namespace vw {
 
+// The forms of the fused inverse, in the order the choice tests them.
+enum class InvForm { kPair, kTwoBuffer, kBlocked, kPlain6, kPlain8, kFullSlab, kOneBuffer };
+
+template <typename T, int L, int NV>
+static InvForm inverse_form(const InvArgs<T>& a) {
+  if (a.pair) return InvForm::kPair;     // pairwise sums: k_inverse_fused
+  if (a.db) return InvForm::kTwoBuffer;  // sequential sums, two LDS buffers: k_inverse_db
+  // register-blocked PERIODIC (host contract; never with NV = 2)
+  if (L > 0 && NV != 2 && a.blk) return InvForm::kBlocked;
+  // full-slab form of the one-buffer sequential kernel (host: InvArgs::full), short filters at NV = 4 ...
+  if (NV == 4 && L > 0 && L <= 8 && a.full) {
+    // ... and its PLAIN form (host: InvArgs::plain; the pointers are the executor's), compiled for 6 or 8 waves per SIMD
+    if (std::is_same<T, double>::value && a.plain && !a.thr && !a.nf_flag && !a.approx_zero && !a.rev)
+      return a.waves == 8 ? InvForm::kPlain8 : InvForm::kPlain6;
+    return InvForm::kFullSlab;
+  }
+  return InvForm::kOneBuffer;  // sequential sums, one LDS buffer: k_inverse_seq
+}
+
 template <typename T, int L, bool FMA, int NV>
 static hipError_t run_inverse_fused_nv(const InvArgs<T>& a, int threads, int lds, hipStream_t st) {
-  // pairwise sums: k_inverse_fused; sequential sums: two LDS buffers (k_inverse_db) or one (k_inverse_seq)
-  static LdsOnce configured_pair, configured_seq, configured_db, configured_blk, configured_full, configured_plain[2];
-  // register-blocked PERIODIC (host contract; never with NV = 2)
-  const bool blk = L > 0 && NV != 2 && a.blk && !a.pair && !a.db;
-  auto k = a.pair ? k_inverse_fused<T, L, FMA, NV> : a.db ? k_inverse_db<T, L, FMA, NV> : k_inverse_seq<T, L, FMA, NV>;
-  if constexpr (NV != 2) {
-    if (blk) k = k_inverse_blk<T, (L > 0 ? L : 2), FMA, NV>;
+  const dim3 grid((unsigned)a.B), block(threads);
+  // the forms that exist only for some (T, L, NV): inverse_form names them for no other
+  constexpr bool kShort = NV == 4 && L > 0 && L <= 8, kF64 = std::is_same<T, double>::value;
+  switch (inverse_form<T, L, NV>(a)) {
+    case InvForm::kPair: return launch_k<k_inverse_fused<T, L, FMA, NV>>(grid, block, lds, st, a);
+    case InvForm::kTwoBuffer: return launch_k<k_inverse_db<T, L, FMA, NV>>(grid, block, lds, st, a);
+    case InvForm::kBlocked:
+      if constexpr (L > 0 && NV != 2) return launch_k<k_inverse_blk<T, L, FMA, NV>>(grid, block, lds, st, a);
+      break;
+    case InvForm::kPlain6:
+      if constexpr (kShort && kF64) return launch_k<k_inverse_seq<T, L, FMA, NV, true, L, 6, true>>(grid, block, lds, st, a);
+      break;
+    case InvForm::kPlain8:
+      if constexpr (kShort && kF64) return launch_k<k_inverse_seq<T, L, FMA, NV, true, L, 8, true>>(grid, block, lds, st, a);
+      break;
+    case InvForm::kFullSlab:
+      if constexpr (kShort) return launch_k<k_inverse_seq<T, L, FMA, NV, true>>(grid, block, lds, st, a);
+      break;
+    case InvForm::kOneBuffer: break;
   }
-  // full-slab form of the one-buffer sequential kernel (host: InvArgs::full), short filters at NV = 4
-  bool full = false;
-  if constexpr (NV == 4 && L > 0 && L <= 8) {
-    full = a.full && !a.pair && !a.db && !blk;
-    if (full) k = k_inverse_seq<T, L, FMA, NV, true>;
-  }
-  // its PLAIN form (host: InvArgs::plain; the pointers are the executor's), compiled for 6 or 8 waves per SIMD
-  LdsOnce* plain = nullptr;
-  if constexpr (NV == 4 && L > 0 && L <= 8 && std::is_same<T, double>::value) {
-    if (full && a.plain && !a.thr && !a.nf_flag && !a.approx_zero && !a.rev) {
-      const bool w8 = a.waves == 8;
-      k = w8 ? k_inverse_seq<T, L, FMA, NV, true, L, 8, true> : k_inverse_seq<T, L, FMA, NV, true, L, 6, true>;
-      plain = &configured_plain[w8];
-    }
-  }
-  hipError_t e = set_lds(k, lds, a.pair ? &configured_pair : a.db ? &configured_db
-                                 : blk ? &configured_blk : plain ? plain : full ? &configured_full : &configured_seq);
-  if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(k, dim3((unsigned)a.B), dim3(threads), lds, st, a);
-  return hipGetLastError();
+  return launch_k<k_inverse_seq<T, L, FMA, NV>>(grid, block, lds, st, a);
 }
 
 template <typename T, int L, bool FMA>
@@ -48,38 +62,24 @@ static hipError_t run_inverse_fused(const InvArgs<T>& a, int threads, int lds, i
 // at its own tap count -- the compile-time pairs of VW_TAP_PAIR_LIST, else the runtime-L kernel with its two counts.
 template <typename T, int L, int LH, bool FMA, int NV>
 static hipError_t run_inverse_bi_nv(const InvArgs<T>& a, int threads, int lds, hipStream_t st) {
-  static LdsOnce configured_seq, configured_db;
-  auto k = a.db ? k_inverse_db<T, L, FMA, NV, LH> : k_inverse_seq<T, L, FMA, NV, false, LH>;
-  hipError_t e = set_lds(k, lds, a.db ? &configured_db : &configured_seq);
-  if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(k, dim3((unsigned)a.B), dim3(threads), lds, st, a);
-  return hipGetLastError();
-}
-template <typename T, int L, int LH>
-static hipError_t run_inverse_bi(const InvArgs<T>& a, int threads, int lds, bool fma, int nv, hipStream_t st) {
-  if (nv <= 4) return fma ? run_inverse_bi_nv<T, L, LH, true, 4>(a, threads, lds, st) : run_inverse_bi_nv<T, L, LH, false, 4>(a, threads, lds, st);
-  return fma ? run_inverse_bi_nv<T, L, LH, true, 8>(a, threads, lds, st) : run_inverse_bi_nv<T, L, LH, false, 8>(a, threads, lds, st);
+  const dim3 grid((unsigned)a.B), block(threads);
+  if (a.db) return launch_k<k_inverse_db<T, L, FMA, NV, LH>>(grid, block, lds, st, a);
+  return launch_k<k_inverse_seq<T, L, FMA, NV, false, LH>>(grid, block, lds, st, a);
 }
 
 template <typename T>
 hipError_t launch_inverse_fused(const InvArgs<T>& a, int threads, int lds, bool fma, int nv, hipStream_t st) {
   if (a.taps_hi != a.taps) {
     if (a.pair || a.blk || nv == 2) return hipErrorInvalidValue;  // not a plan of the two-length route
-    if (a.unrolled) {
-#define VW_CASE(lo, hi) if (a.taps == lo && a.taps_hi == hi) return run_inverse_bi<T, lo, hi>(a, threads, lds, fma, nv, st);
-      VW_TAP_PAIR_LIST(VW_CASE)
-#undef VW_CASE
-    }
-    return run_inverse_bi<T, 0, 0>(a, threads, lds, fma, nv, st);
+    return dispatch_tap_pair(a.unrolled, a.taps, a.taps_hi, fma, [&](auto l, auto lh, auto m) {
+      return nv <= 4 ? run_inverse_bi_nv<T, l(), lh(), m(), 4>(a, threads, lds, st)
+                     : run_inverse_bi_nv<T, l(), lh(), m(), 8>(a, threads, lds, st);
+    });
   }
-  switch (a.unrolled ? a.taps : 0) {  // unaligned rows / partial slabs: runtime-L kernel
-#define VW_CASE(n) \
-    case n: return fma ? run_inverse_fused<T, n, true>(a, threads, lds, nv, st) : run_inverse_fused<T, n, false>(a, threads, lds, nv, st);
-    VW_TAP_LIST(VW_CASE)
-#undef VW_CASE
-    default:
-      return fma ? run_inverse_fused<T, 0, true>(a, threads, lds, nv, st) : run_inverse_fused<T, 0, false>(a, threads, lds, nv, st);
-  }
+  // unaligned rows / partial slabs: runtime-L kernel
+  return dispatch_taps<Unlisted::kRuntimeL>(a.unrolled ? a.taps : 0, fma, [&](auto l, auto m) {
+    return run_inverse_fused<T, l(), m()>(a, threads, lds, nv, st);
+  });
 }
 template hipError_t launch_inverse_fused<VW_T>(const InvArgs<VW_T>&, int, int, bool, int, hipStream_t);
 }  // namespace vw

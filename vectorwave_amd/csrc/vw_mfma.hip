@@ -27,7 +27,8 @@
 // Scope: PERIODIC, fp32, VW_FLAG_FMA (EXACT keeps the VALU kernels: separate multiply and add), one signal
 // per workgroup (NT threads, N = 4 * NT * TPW samples, TPW tiles per wave), every level's halo (4*KS - 16)*s
 // within the row.  Host policy: vw_plan.cpp mfma_layout (VW_MFMA).
-#include "vw_device.h"
+#include "vw_launch_k.h"
+#include "vw_dev_core.h"
 
 namespace vw {
 
@@ -321,22 +322,12 @@ __global__ void __launch_bounds__(NT) k_inverse_mfma(const InvArgs<float> p) {
 // p.tap_lds = the tap table's element offset.  L = 30 (coif5) and 16 (db8 / sym8) are instantiated.
 template <int L, int TPW, int NT>
 static hipError_t run_fwd(const FwdArgs<float>& a, int lds, hipStream_t st) {
-  auto k = k_forward_mfma<L, TPW, NT>;
-  static LdsOnce configured;
-  hipError_t e = set_lds(k, lds, &configured);
-  if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(k, dim3((unsigned)a.B), dim3(NT), lds, st, a);
-  return hipGetLastError();
+  return launch_k<k_forward_mfma<L, TPW, NT>>(dim3((unsigned)a.B), dim3(NT), lds, st, a);
 }
 
 template <int L, int TPW, int NT>
 static hipError_t run_inv(const InvArgs<float>& a, int lds, hipStream_t st) {
-  auto k = k_inverse_mfma<L, TPW, NT>;
-  static LdsOnce configured;
-  hipError_t e = set_lds(k, lds, &configured);
-  if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(k, dim3((unsigned)a.B), dim3(NT), lds, st, a);
-  return hipGetLastError();
+  return launch_k<k_inverse_mfma<L, TPW, NT>>(dim3((unsigned)a.B), dim3(NT), lds, st, a);
 }
 
 #define VW_MFMA_DISPATCH(RUN, a, lds, st)                                    \

@@ -15,7 +15,8 @@
 // Two LDS regions, used ping-pong: a pass reads one region while its sums -- the next level's input, halo
 // included -- go to the other, so every pass costs ONE workgroup barrier (k_inverse_db's pattern).  The next
 // component's input row is prefetched into registers while the current chain computes.
-#include "vw_launch.h"
+#include "vw_launch_k.h"
+#include "vw_dev_rows.h"
 
 namespace vw {
 
@@ -62,39 +63,17 @@ __global__ void VW_FUSED_BOUNDS(NV, VW_FUSED_W(L, 6)) k_mra(const MraArgs<T> p) 
   }
 }
 
-template <typename T, int L, bool FMA, int NV>
-static hipError_t run_mra_nv(const MraArgs<T>& a, int threads, int lds, int grid, hipStream_t st) {
-  auto k = k_mra<T, L, FMA, NV>;
-  static LdsOnce configured;
-  hipError_t e = set_lds(k, lds, &configured);
-  if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(k, dim3((unsigned)grid), dim3(threads), lds, st, a);
-  return hipGetLastError();
-}
-
-template <typename T, int L, bool FMA>
-static hipError_t run_mra(const MraArgs<T>& a, int threads, int lds, int nv, int grid, hipStream_t st) {
-  return nv <= 4 ? run_mra_nv<T, L, FMA, 4>(a, threads, lds, grid, st) : run_mra_nv<T, L, FMA, 8>(a, threads, lds, grid, st);
-}
-
 template <typename T>
 hipError_t launch_mra(const MraArgs<T>& a, int threads, int lds, bool fma, int nv, int grid, hipStream_t st) {
   if (threads <= 0 || threads % 64 != 0 || grid <= 0 || (nv != 4 && nv != 8)) return hipErrorInvalidConfiguration;
-  // Tap-unrolled bodies up to kMraUnrollMax (the energy unit's precedent); longer and unlisted filters,
+  auto run = [&](auto l, auto m) {
+    if (nv <= 4) return launch_k<k_mra<T, l(), m(), 4>>(dim3((unsigned)grid), dim3(threads), lds, st, a);
+    return launch_k<k_mra<T, l(), m(), 8>>(dim3((unsigned)grid), dim3(threads), lds, st, a);
+  };
+  // Tap-unrolled bodies up to kMraUnrollMax (the energy unit's precedent; plan_mra names no kernel this unit lacks);
   // unaligned rows and partial slabs take the runtime-L body.
-  switch (a.unrolled ? a.taps : 0) {
-#define VW_CASE(n)                                                                    \
-    case n:                                                                           \
-      if constexpr (n <= kMraUnrollMax)                                               \
-        return fma ? run_mra<T, n, true>(a, threads, lds, nv, grid, st)               \
-                   : run_mra<T, n, false>(a, threads, lds, nv, grid, st);             \
-      break;
-    VW_TAP_LIST(VW_CASE)
-#undef VW_CASE
-    default: break;
-  }
-  if (a.unrolled) return hipErrorInvalidConfiguration;  // plan_mra names no kernel this unit lacks
-  return fma ? run_mra<T, 0, true>(a, threads, lds, nv, grid, st) : run_mra<T, 0, false>(a, threads, lds, nv, grid, st);
+  if (a.unrolled) return dispatch_taps<Unlisted::kInvalidConfiguration, kMraUnrollMax>(a.taps, fma, run);
+  return with_fma(fma, [&](auto m) { return run(std::integral_constant<int, 0>{}, m); });
 }
 template hipError_t launch_mra<VW_T>(const MraArgs<VW_T>&, int, int, bool, int, int, hipStream_t);
 

@@ -36,7 +36,9 @@
 // (L - 1) * 2^(J-1) rounded: pair_fusable checks it) -- the size is the maximum of the two needs, not their sum.
 // Registers: 4 waves per SIMD (128 VGPRs) as the forward; the halves are sequential.  A kept plane is 16 VGPRs:
 // KEEP = 2 takes 124-125 of the 128 at L = 8, a third plane spills.
-#include "vw_device.h"
+#include "vw_launch_k.h"
+#include "vw_dev_fwd.h"
+#include "vw_dev_inv.h"
 
 #include <algorithm>
 #include <mutex>
@@ -116,19 +118,15 @@ static PairKernel* pair_kernel_keep(int keep) {
 
 static PairKernel* pair_kernel(int taps, bool fma, int keep) {
   if (keep < 0 || keep > kPairMaxKeep) return nullptr;
-  switch (taps) {
-#define VW_CASE(n) \
-    case n:        \
-      if constexpr (n <= kPairMaxTaps) return fma ? pair_kernel_keep<n, true>(keep) : pair_kernel_keep<n, false>(keep); \
-      break;
-    VW_TAP_LIST(VW_CASE)
-#undef VW_CASE
-    default: break;
-  }
-  return nullptr;
+  PairKernel* k = nullptr;  // stays null for an unlisted count, or one above kPairMaxTaps
+  (void)dispatch_taps<Unlisted::kNotSupported, kPairMaxTaps>(taps, fma, [&](auto l, auto m) {
+    k = pair_kernel_keep<l(), m()>(keep);
+    return hipSuccess;
+  });
+  return k;
 }
 
-// the dynamic-LDS limit of this device's copy of the kernel covers `lds` (set_lds)
+// the dynamic-LDS limit of this device's copy of the kernel covers `lds` (vw_launch_k.h set_lds)
 static bool lds_ready(PairKernel* k, int lds) {
   if (lds <= 64 * 1024) return true;
   int dev = 0;

@@ -223,7 +223,7 @@ static bool fused_plan(const Tuning& tu, int64_t N, int V, int elem, int64_t lds
   return true;
 }
 
-// Owner-written halo of one level (vw_device.h halo_images): the affine images of an element and
+// Owner-written halo of one level (vw_dev_core.h halo_images): the affine images of an element and
 // the vector bands that have them; `own` only when every band lies in the slab that checks it.
 static void set_halo_images(LevelDesc& d, int64_t N, int64_t npow2, int V, int threads, int nv) {
   int64_t s_el = 0, e_el = N;
@@ -306,7 +306,7 @@ static int mfma_layout(bool ok, int L, int J, int64_t N, int scratch, int* halo,
   return (reg + 2 * L + scratch) * 4;
 }
 
-// Level groups of the per-level path (vw_device.h k_forward_multi / k_inverse_multi): from level 1
+// Level groups of the per-level path (vw_dev_lvl.h k_forward_multi / k_inverse_multi): from level 1
 // up, consecutive PERIODIC levels run as one multi-level tile launch while their combined reach
 // sum((L-1)*s_j) stays within a quarter of the tile (the redundant arithmetic).  g[j-1] = size
 // of the group starting at level j (0 inside a group, 1 = the per-level kernels).  VW_MULTI=0
@@ -341,7 +341,7 @@ static void level_groups(const Tuning& tu, const LevelDesc* lv, int J, int L, in
   }
 }
 
-// Level group of the chained column sweeps (vw_device.h k_inverse_sweep2 / k_inverse_sweep3): inverse levels
+// Level group of the chained column sweeps (vw_dev_lvl.h k_inverse_sweep2 / k_inverse_sweep3): inverse levels
 // j .. j-levels+1 (spacings G*h .. h, G = 2 / 4), all column-sweep levels outside the multi-level tile
 // groups, PERIODIC / dir +1 / offset 0.  Picks KA (outputs per thread and step) and R (residues per
 // group, 64 or 32 = h's alignment) under the kernels' rules: a block of G*KA positions covers the
@@ -500,7 +500,7 @@ static int forward_levels(const FwdCall<T>& c, LevelDesc* lv, int Llo = 0, int L
 // EXACT kernel is faster with one buffer (more workgroups to overlap its longer arithmetic).
 // VW_FWD_BUF=1|2 overrides.
 //
-// Persistent variant (vw_device.h k_forward_persist): next row by LDS-DMA during the last level.
+// Persistent variant (vw_dev_fwd.h k_forward_persist): next row by LDS-DMA during the last level.
 // Its contract: two buffers, full slabs of whole waves, rows in 64-vector chunks, no validation
 // or streaming history.  VW_FWD_PERSIST=0 disables it.
 template <typename T>
@@ -809,7 +809,7 @@ static void inverse_levels(const InvCall<T>& c, int Llo, int Lhi, LevelDesc* lv,
   }
 }
 
-// The PLAIN class of inverse calls (vw_device.h inverse_seq_plain): a full-slab fp64 PERIODIC reconstruction of a short
+// The PLAIN class of inverse calls (vw_dev_inv.h inverse_seq_plain): a full-slab fp64 PERIODIC reconstruction of a short
 // filter from every coefficient plane, forward walk, no threshold, no probe -- every level reads t + i*s with no
 // left halo and a right one within the row.  Independent of the LDS buffer count: plan_inverse_fused marks
 // k_inverse_seq plans of the class (InvArgs::plain), pair_fusable also takes k_inverse_db plans of it.  Reads
@@ -901,7 +901,7 @@ static bool plan_inverse_fused(const Tuning& tu, const InvCall<T>& c, bool pair,
   // VW_FLAG_REF_NONFINITE: the one-buffer sequential kernels (k_inverse_seq / k_inverse_blk, vw_inv.hip's
   // choice) probe their output themselves (no scan pass afterwards)
   p->nf_probed = p->ref_nf && (p->kernel == kInvSeq || p->kernel == kInvBlk);
-  // k_inverse_seq's PLAIN form (vw_device.h inverse_seq_plain; fp64 short filters, vw_inv.hip's dispatch): a
+  // k_inverse_seq's PLAIN form (vw_dev_inv.h inverse_seq_plain; fp64 short filters, vw_inv.hip's dispatch): a
   // full-slab PERIODIC reconstruction that uses none of the general form's optional state
   a.plain = p->kernel == kInvSeq && plain_class(c, *p, nv) ? 1 : 0;
   a.waves = tu.inv_waves;
@@ -922,14 +922,14 @@ static void inverse_multi_layout(const Tuning& tu, const LevelDesc* lv, int j0, 
   m.rblk = tu.multi_rblk;
   // register prefetch of d_{j-1} while level j computes: whole vectors, every tile of the group
   m.pf = tu.multi_pf && m.vec_io && (int64_t)(mtile + m.ext[g - 1]) / V <= (int64_t)kMultiPF * 256;
-  // padded layout at the register-blocked levels (vw_device.h k_inverse_multi): needs the register
+  // padded layout at the register-blocked levels (vw_dev_lvl.h k_inverse_multi): needs the register
   // paths (prefetch, blocked taps); the regions grow by one vector in eight
   m.pad = tu.multi_pad && m.pf && m.rblk && has_unrolled_taps(L);
   if (m.pad) {
     const int nvmax = (mtile + m.ext[g - 1]) / V + 1;
     m.region = (nvmax + nvmax / 8 + 1) * V;
   }
-  // slack past D for the compile-time-stride reads (vw_device.h k_inverse_multi): 15*M <= 120 vectors
+  // slack past D for the compile-time-stride reads (vw_dev_lvl.h k_inverse_multi): 15*M <= 120 vectors
   m.slack = 160;
   m.ni = kMultiInvNI;
   if (tu.multi_ni == 4 && sizeof(T) == 8 && m.pad) {

@@ -1,6 +1,6 @@
 // vw_plan.h -- kernel selection of the forward and inverse transforms, as a pure host function of the
 // call's shape, flags and pointer alignments, the tuning switches and the CU count.  plan_forward /
-// plan_inverse make no HIP call and touch no memory behind the caller's pointers; vw_capi.cpp executes
+// plan_inverse make no HIP call and touch no memory behind the caller's pointers; vw_exec.cpp executes
 // what they return (reserve, launch, fix up) and decides nothing itself.  Compiles with a plain C++
 // compiler (tests/plan_harness checks every plan against the kernels' launch contracts on the CPU).
 #pragma once
@@ -74,7 +74,7 @@ struct Tuning {
   int mra_fused = 1;           // VW_MRA_FUSED=0: vw_mra_planes_* / vw_modwt_mra_* never run k_mra (J+1 masked inverses instead);
                                // 2: k_mra wherever it fits, also where it measured slower than the loop (plan_mra)
   int pair_fuse = 1;           // VW_PAIR_FUSE=0: a captured forward and the inverse that follows it stay two kernels;
-                               // 1: one k_roundtrip launch where pair_fusable holds (vw_capi.cpp)
+                               // 1: one k_roundtrip launch where pair_fusable holds (vw_exec.cpp)
   int pair_keep = -1;          // VW_PAIR_KEEP=0|1|2: k_roundtrip keeps that many detail planes below d_J in registers instead
                                // of reading them back (larger values: 2); < 0: auto, see pair_keep_variant (vw_internal.h)
   int bi_listed = 1;           // VW_BI_LISTED=0: a two-length bank runs max(Llo, Lhi) taps even where that count is not in
@@ -260,7 +260,7 @@ void plan_cwt(const CwtCall& c, CwtPlan* p);
 // SYMMETRIC shifts tau(L) / tau(Lhi) per branch, halos over the longer reach.  The pairwise inverses (single
 // level, ZERO_PADDING) loop over l < L and read hi[l]: args.taps = L with hi truncated when Lhi >= L,
 // VW_ERR_UNSUPPORTED when Lhi < L (the reference indexes past its high-pass array).  The executor copies the
-// taps accordingly (vw_capi.cpp copy_bank).
+// taps accordingly (vw_host.h copy_bank).
 // TWO-LENGTH ROUTE (VW_BI): where the non-persistent fused forward (k_forward_fused, no history) or the fused
 // sequential-sum inverse (k_inverse_seq / k_inverse_db) fits at NV = 4 / 8, args.taps = L and args.taps_hi = Lhi.  The
 // forward reads each tap position once and feeds the low sum while i < L, the high sum while i < Lhi; each inverse

@@ -28,7 +28,7 @@
 // the level input from global memory (L2).  Flags stay zero between calls: these kernels clear every row
 // they recompute.
 #include <hip/hip_runtime.h>
-#include "vw_internal.h"
+#include "vw_launch_k.h"
 
 #pragma clang fp contract(off)
 
@@ -217,15 +217,13 @@ hipError_t launch_flag_nonfinite(const RefScan<T>& a, hipStream_t st) {
   const long long grid = a.B * (long long)a.chunks;
   if (grid <= 0) return hipSuccess;
   if (grid > 0x7fffffffLL) return hipErrorInvalidConfiguration;
-  hipLaunchKernelGGL(k_flag_nonfinite<T>, dim3((unsigned)grid), dim3(kScanThreads), 0, st, a);
-  return hipGetLastError();
+  return launch_k<k_flag_nonfinite<T>>(dim3((unsigned)grid), dim3(kScanThreads), 0, st, a);
 }
 
 template <typename T>
 hipError_t launch_ref_cascade(const RefArgs<T>& a, int grid, bool inverse, hipStream_t st) {
-  if (inverse) hipLaunchKernelGGL(k_ref_inverse<T>, dim3((unsigned)grid), dim3(512), 0, st, a);
-  else hipLaunchKernelGGL(k_ref_forward<T>, dim3((unsigned)grid), dim3(512), 0, st, a);
-  return hipGetLastError();
+  if (inverse) return launch_k<k_ref_inverse<T>>(dim3((unsigned)grid), dim3(512), 0, st, a);
+  return launch_k<k_ref_forward<T>>(dim3((unsigned)grid), dim3(512), 0, st, a);
 }
 
 int ref_scan_chunks(int N) { return (N + kScanChunk - 1) / kScanChunk; }

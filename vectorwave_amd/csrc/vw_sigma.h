@@ -1,6 +1,6 @@
 // vw_sigma.h -- per-signal noise estimate for the SWT denoise path (included by vw_misc.hip only).
 #pragma once
-#include "vw_device.h"
+#include "vw_dev_core.h"
 
 namespace vw {
 
