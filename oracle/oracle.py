@@ -12,7 +12,7 @@ import ctypes
 import math
 import os
 import subprocess
-from ctypes import POINTER, c_double, c_int, c_longlong, c_uint, c_ulonglong, c_void_p
+from ctypes import POINTER, c_double, c_float, c_int, c_longlong, c_uint, c_ulonglong, c_void_p
 
 import numpy as np
 
@@ -21,6 +21,7 @@ LIB = os.path.join(_HERE, "libvw_oracle.so")
 
 PERIODIC, SYMMETRIC, ZERO_PADDING = 0, 1, 2
 _dp = POINTER(c_double)
+_fp = POINTER(c_float)
 
 
 def build() -> str:
@@ -78,6 +79,8 @@ def lib() -> ctypes.CDLL:
                                           c_int, _dp]),
             "vwo_fill_uniform": (None, [_dp, c_longlong, c_ulonglong, c_longlong]),
             "vwo_first_nonfinite": (c_longlong, [_dp, c_longlong]),
+            "vwo_fma_f64": (None, [_dp, c_double, _dp, c_longlong, _dp]),
+            "vwo_fma_f32": (None, [_fp, c_float, _fp, c_longlong, _fp]),
         }
         for name, (res, args) in sig.items():
             f = getattr(L, name)
@@ -300,6 +303,29 @@ def batch_denoise(x: np.ndarray, lo, hi, boundary: int, levels: int, thr: float 
 def fill_uniform(count: int, seed: int = 42, offset: int = 0) -> np.ndarray:
     out = np.empty(count)
     lib().vwo_fill_uniform(_p(out), count, seed, offset)
+    return out
+
+
+def fma_f64(x, f, acc) -> np.ndarray:
+    """Element-wise ``fma(x, f, acc)`` in binary64, one rounding (libm ``fma``); ``f`` a scalar, ``x`` and ``acc``
+    broadcast to one shape."""
+    x, acc = np.broadcast_arrays(np.asarray(x, dtype=np.float64), np.asarray(acc, dtype=np.float64))
+    x, acc = np.ascontiguousarray(x), np.ascontiguousarray(acc)
+    out = np.empty(x.shape, dtype=np.float64)
+    lib().vwo_fma_f64(_p(x), float(f), _p(acc), x.size, _p(out))
+    return out
+
+
+def fma_f32(x, f, acc) -> np.ndarray:
+    """Element-wise ``fmaf(x, f, acc)`` in binary32, one rounding (libm ``fmaf``, not a binary64 detour, which
+    rounds twice).  ``f`` must be a binary32 value."""
+    x, acc = np.broadcast_arrays(np.asarray(x, dtype=np.float32), np.asarray(acc, dtype=np.float32))
+    x, acc = np.ascontiguousarray(x), np.ascontiguousarray(acc)
+    f32 = np.float32(f)
+    if float(f32) != float(f):
+        raise ValueError("fma_f32: the tap is not a binary32 value")
+    out = np.empty(x.shape, dtype=np.float32)
+    lib().vwo_fma_f32(x.ctypes.data_as(_fp), float(f32), acc.ctypes.data_as(_fp), x.size, out.ctypes.data_as(_fp))
     return out
 
 

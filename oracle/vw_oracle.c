@@ -879,3 +879,18 @@ void vwo_fill_uniform(double *x, long long count, unsigned long long seed, long 
         x[i] = 2.0 * u - 1.0;
     }
 }
+
+/* Correctly rounded fused multiply-add, element-wise: out[i] = fma(x[i], f, acc[i]) with ONE rounding (libm
+ * fma / fmaf; explicit calls, which -ffp-contract=off leaves alone).  The accumulate step of the engine's FMA
+ * mode (madd<FMA> in vw_dev_core.h), for the numpy restatements under tests/. */
+void vwo_fma_f64(const double *x, double f, const double *acc, long long count, double *out)
+{
+    for (long long i = 0; i < count; i++)
+        out[i] = fma(x[i], f, acc[i]);
+}
+
+void vwo_fma_f32(const float *x, float f, const float *acc, long long count, float *out)
+{
+    for (long long i = 0; i < count; i++)
+        out[i] = fmaf(x[i], f, acc[i]);
+}

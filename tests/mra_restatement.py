@@ -9,7 +9,9 @@ input is not a zeroed plane,
     component 0      low-pass passes at levels J .. 1 on approx
     component c > 0  one high-pass pass at level c on d_c, then low-pass passes at levels c-1 .. 1
 
-each pass ``acc = 0; acc = acc + f[l] * src[index_l(t)]`` in ascending tap order.  Every accumulator starts at +0.0
+each pass ``acc = 0; acc = acc + f[l] * src[index_l(t)]`` in ascending tap order (``fma=True``: the FMA mode's
+``acc = fma(src, f[l], acc)``, restatement_generic.accumulate -- k_mra's sums; see ``mra_by_masks`` for the loop
+path's).  Every accumulator starts at +0.0
 and a sum of finite terms that started at +0.0 is never -0.0, so the skipped ``acc + f * (+-0)`` steps -- and the
 zero partner of the ZERO_PADDING pairwise term ``lo * a + hi * 0`` -- could not have changed a bit
 (tests/test_mra_restatement_cpu.py compares the two forms byte for byte, signed zeros included).
@@ -19,10 +21,10 @@ from __future__ import annotations
 import numpy as np
 
 from oracle import oracle as O
-from restatement_generic import PERIODIC, SYMMETRIC, ZERO_PADDING, _sym_index, reconstruct, scaled_taps
+from restatement_generic import PERIODIC, SYMMETRIC, ZERO_PADDING, _sym_index, accumulate, reconstruct, scaled_taps
 
 
-def _branch_pass(src, f, s, boundary, plus, tau):
+def _branch_pass(src, f, s, boundary, plus, tau, fma=False):
     """One branch of one level: periodic / zero padding read t + l*s; symmetric reads t + l*s - tau (plus) or
     t - l*s + tau through the mirror."""
     n = src.shape[-1]
@@ -30,14 +32,14 @@ def _branch_pass(src, f, s, boundary, plus, tau):
     acc = np.zeros_like(src)
     for l in range(len(f)):
         if boundary == PERIODIC:
-            acc = acc + f[l] * src[..., np.mod(t + l * s, n)]
+            acc = accumulate(acc, src[..., np.mod(t + l * s, n)], f[l], fma)
         elif boundary == ZERO_PADDING:
             idx = t + l * s
             ok = idx < n
-            acc = np.where(ok, acc + f[l] * src[..., np.where(ok, idx, 0)], acc)
+            acc = accumulate(acc, src[..., np.where(ok, idx, 0)], f[l], fma, ok)
         else:
             idx = t + l * s - tau if plus else t - l * s + tau
-            acc = acc + f[l] * src[..., _sym_index(idx, n)]
+            acc = accumulate(acc, src[..., _sym_index(idx, n)], f[l], fma)
     return acc
 
 
@@ -50,7 +52,7 @@ def _align(boundary, wavelet_id, L, j):
     return ap, tau + dh, dp, tau + dg
 
 
-def component(det, app, lo, hi, boundary: int, c: int, wavelet_id: int = 0, dtype=np.float64):
+def component(det, app, lo, hi, boundary: int, c: int, wavelet_id: int = 0, dtype=np.float64, fma: bool = False):
     """Component c (0 = smooth, j = detail level j) of det [J, (B,) N] / app [(B,) N], in ``dtype``."""
     dtype = np.dtype(dtype).type
     det = np.ascontiguousarray(np.asarray(det), dtype=dtype)
@@ -65,21 +67,25 @@ def component(det, app, lo, hi, boundary: int, c: int, wavelet_id: int = 0, dtyp
         cur, top = app, J
     else:
         ap, th, dp, tg = _align(boundary, wavelet_id, L, c)
-        cur, top = _branch_pass(det[c - 1], fhi, 1 << (c - 1), boundary, dp, tg), c - 1
+        cur, top = _branch_pass(det[c - 1], fhi, 1 << (c - 1), boundary, dp, tg, fma), c - 1
     for j in range(top, 0, -1):
         ap, th, dp, tg = _align(boundary, wavelet_id, L, j)
-        cur = _branch_pass(cur, flo, 1 << (j - 1), boundary, ap, th)
+        cur = _branch_pass(cur, flo, 1 << (j - 1), boundary, ap, th, fma)
     return cur
 
 
-def mra(det, app, lo, hi, boundary: int, wavelet_id: int = 0, dtype=np.float64):
+def mra(det, app, lo, hi, boundary: int, wavelet_id: int = 0, dtype=np.float64, fma: bool = False):
     """All J+1 components, [J+1, (B,) N]: row 0 the smooth, row j detail component j."""
     J = np.asarray(det).shape[0]
-    return np.stack([component(det, app, lo, hi, boundary, c, wavelet_id, dtype) for c in range(J + 1)])
+    return np.stack([component(det, app, lo, hi, boundary, c, wavelet_id, dtype, fma) for c in range(J + 1)])
 
 
-def mra_by_masks(det, app, lo, hi, boundary: int, wavelet_id: int = 0, dtype=np.float64):
-    """The definition: J+1 masked reconstructions (restatement_generic.reconstruct)."""
+def mra_by_masks(det, app, lo, hi, boundary: int, wavelet_id: int = 0, dtype=np.float64, fma: bool = False):
+    """The definition: J+1 masked reconstructions (restatement_generic.reconstruct) -- also the sequence of the
+    engine's LOOP PATH (J+1 masked inverses).  In FMA mode it equals ``mra`` for PERIODIC and SYMMETRIC
+    (``fma(+-0, f, acc) == acc``); for ZERO_PADDING it does not: the masked pairwise term
+    ``acc + fma(lo, a, round(hi * 0))`` rounds the product before the add, where the fused kernel's branch pass is
+    ``fma(a, lo, acc)``."""
     J = np.asarray(det).shape[0]
-    return np.stack([reconstruct(det, app, lo, hi, boundary, wavelet_id, (1 << (c - 1)) if c else 0, c != 0, dtype)
+    return np.stack([reconstruct(det, app, lo, hi, boundary, wavelet_id, (1 << (c - 1)) if c else 0, c != 0, dtype, fma)
                      for c in range(J + 1)])

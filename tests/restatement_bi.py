@@ -14,7 +14,8 @@ BiorthogonalSpline / ReverseBiorthogonalSpline (paths under vectorwave-core/src/
                      ``fft=True`` in ``decompose`` applies that index map to them.
 
 Arithmetic as restatement_generic: ``acc = acc + x * f`` per tap, product rounded then sum rounded, taps
-``dtype(h * (1 / sqrt(2)))``.  Only the base taps are visited (zero taps of the upsampled filter leave a finite sum
+``dtype(h * (1 / sqrt(2)))``; ``fma=True`` switches every step to the FMA mode's (``accumulate`` /
+``accumulate_pair`` of restatement_generic: ``fma(x, f, acc)`` and ``acc + fma(lo, a, round(hi * d))``).  Only the base taps are visited (zero taps of the upsampled filter leave a finite sum
 unchanged); ``decompose_full`` / ``reconstruct_full`` visit every upsampled tap, zeros included, in the reference's
 order -- the non-finite semantics.
 """
@@ -23,7 +24,7 @@ from __future__ import annotations
 import numpy as np
 
 from oracle import oracle as O
-from restatement_generic import _sym_index, scaled_taps
+from restatement_generic import _sym_index, accumulate, accumulate_pair, scaled_taps
 
 PERIODIC, SYMMETRIC, ZERO_PADDING = O.PERIODIC, O.SYMMETRIC, O.ZERO_PADDING
 
@@ -41,7 +42,7 @@ def fft_modes(n: int, Llo: int, Lhi: int, j: int):
     return (n >= 1024 and llo > n * (1.0 / 8.0) and not pow2, n >= 1024 and lhi > n * (1.0 / 8.0) and not pow2)
 
 
-def _conv(cur, f, s, boundary, fft_pad=False):
+def _conv(cur, f, s, boundary, fft_pad=False, fma=False):
     """One filter over one level input: out[t] = sum_l f[l] * x[index(t - l*s)], ascending l."""
     n = cur.shape[-1]
     t = np.arange(n)
@@ -53,18 +54,18 @@ def _conv(cur, f, s, boundary, fft_pad=False):
             idx = np.mod(idx, npow2)
             ok = idx < n
             src = cur[..., np.where(ok, idx, 0)]
-            acc = acc + np.where(ok, src, np.zeros_like(src)) * f[l]
+            acc = accumulate(acc, np.where(ok, src, np.zeros_like(src)), f[l], fma)
         elif boundary == PERIODIC:
-            acc = acc + cur[..., np.mod(idx, n)] * f[l]
+            acc = accumulate(acc, cur[..., np.mod(idx, n)], f[l], fma)
         elif boundary == ZERO_PADDING:
             ok = idx >= 0
-            acc = np.where(ok, acc + cur[..., np.where(ok, idx, 0)] * f[l], acc)
+            acc = accumulate(acc, cur[..., np.where(ok, idx, 0)], f[l], fma, ok)
         else:
-            acc = acc + cur[..., _sym_index(idx, n)] * f[l]
+            acc = accumulate(acc, cur[..., _sym_index(idx, n)], f[l], fma)
     return acc
 
 
-def decompose(x, lo, hi, boundary: int, levels: int, dtype=np.float64, fft: bool = False):
+def decompose(x, lo, hi, boundary: int, levels: int, dtype=np.float64, fft: bool = False, fma: bool = False):
     """x [N] or [B, N] -> (details [J, (B,) N], approx [(B,) N]); ``lo`` / ``hi`` the ANALYSIS pair."""
     dtype = np.dtype(dtype).type
     cur = np.ascontiguousarray(np.asarray(x), dtype=dtype)
@@ -76,19 +77,20 @@ def decompose(x, lo, hi, boundary: int, levels: int, dtype=np.float64, fft: bool
     for j in range(1, levels + 1):
         s = 1 << (j - 1)
         f_lo, f_hi = fft_modes(n, len(lo), len(hi), j) if (fft and boundary == PERIODIC) else (False, False)
-        det[j - 1] = _conv(cur, fhi, s, boundary, f_hi)
-        cur = _conv(cur, flo, s, boundary, f_lo)
+        det[j - 1] = _conv(cur, fhi, s, boundary, f_hi, fma)
+        cur = _conv(cur, flo, s, boundary, f_lo, fma)
     return det, cur
 
 
-def forward1(x, lo, hi, boundary: int, dtype=np.float64):
+def forward1(x, lo, hi, boundary: int, dtype=np.float64, fma: bool = False):
     """MODWTTransform.forward: (approx, detail), any N >= 1."""
     dtype = np.dtype(dtype).type
     cur = np.ascontiguousarray(np.asarray(x), dtype=dtype)
-    return (_conv(cur, scaled_taps(lo, dtype), 1, boundary), _conv(cur, scaled_taps(hi, dtype), 1, boundary))
+    return (_conv(cur, scaled_taps(lo, dtype), 1, boundary, fma=fma),
+            _conv(cur, scaled_taps(hi, dtype), 1, boundary, fma=fma))
 
 
-def _pairwise(a, d, flo, fhi, s, index):
+def _pairwise(a, d, flo, fhi, s, index, fma=False):
     """acc += lo[l] * a[idx] + hi[l] * d[idx] over l < Llo, reading high[l] (the reference's truncation / throw)."""
     if len(fhi) < len(flo):
         raise IndexError(f"Index {len(fhi)} out of bounds for length {len(fhi)}")  # Java's exception at l = Lhi
@@ -97,8 +99,7 @@ def _pairwise(a, d, flo, fhi, s, index):
     acc = np.zeros_like(a)
     for l in range(len(flo)):
         ok, src = index(t, l * s, n)
-        term = flo[l] * a[..., src] + fhi[l] * d[..., src]
-        acc = acc + term if ok is None else np.where(ok, acc + term, acc)
+        acc = accumulate_pair(acc, a[..., src], flo[l], d[..., src], fhi[l], fma, ok)
     return acc
 
 
@@ -108,25 +109,25 @@ def _idx_zero(t, off, n):
     return ok, np.where(ok, idx, 0)
 
 
-def _inverse_level(a, d, flo, fhi, s, boundary, align):
+def _inverse_level(a, d, flo, fhi, s, boundary, align, fma=False):
     n = a.shape[-1]
     t = np.arange(n)
     if boundary == ZERO_PADDING:
-        return _pairwise(a, d, flo, fhi, s, _idx_zero)
+        return _pairwise(a, d, flo, fhi, s, _idx_zero, fma)
     acc = np.zeros_like(a)
     if boundary == PERIODIC:
         for l in range(len(flo)):
-            acc = acc + flo[l] * a[..., np.mod(t + l * s, n)]
+            acc = accumulate(acc, a[..., np.mod(t + l * s, n)], flo[l], fma)
         for l in range(len(fhi)):
-            acc = acc + fhi[l] * d[..., np.mod(t + l * s, n)]
+            acc = accumulate(acc, d[..., np.mod(t + l * s, n)], fhi[l], fma)
         return acc
     approx_plus, tau_h, detail_plus, tau_g = align
     for l in range(len(flo)):
         idx = t + l * s - tau_h if approx_plus else t - l * s + tau_h
-        acc = acc + flo[l] * a[..., _sym_index(idx, n)]
+        acc = accumulate(acc, a[..., _sym_index(idx, n)], flo[l], fma)
     for l in range(len(fhi)):
         idx = t + l * s - tau_g if detail_plus else t - l * s + tau_g
-        acc = acc + fhi[l] * d[..., _sym_index(idx, n)]
+        acc = accumulate(acc, d[..., _sym_index(idx, n)], fhi[l], fma)
     return acc
 
 
@@ -136,7 +137,7 @@ def sym_align(wavelet_id: int, Llo: int, Lhi: int, j: int):
 
 
 def reconstruct(det, app, lo, hi, boundary: int, wavelet_id: int = 0, detail_mask: int = 0xFFFFFFFF,
-                approx_zero: bool = False, dtype=np.float64):
+                approx_zero: bool = False, dtype=np.float64, fma: bool = False):
     """det [J, (B,) N], app [(B,) N] -> y; ``lo`` / ``hi`` the SYNTHESIS pair."""
     dtype = np.dtype(dtype).type
     det = np.ascontiguousarray(np.asarray(det), dtype=dtype)
@@ -151,11 +152,11 @@ def reconstruct(det, app, lo, hi, boundary: int, wavelet_id: int = 0, detail_mas
     for j in range(J, 0, -1):
         align = sym_align(wavelet_id, len(lo), len(hi), j) if boundary == SYMMETRIC else None
         d = det[j - 1] if (detail_mask >> (j - 1)) & 1 else zero
-        cur = _inverse_level(cur, d, flo, fhi, 1 << (j - 1), boundary, align)
+        cur = _inverse_level(cur, d, flo, fhi, 1 << (j - 1), boundary, align, fma)
     return cur
 
 
-def inverse1(approx, detail, lo, hi, boundary: int, batch_sym: bool = False, dtype=np.float64):
+def inverse1(approx, detail, lo, hi, boundary: int, batch_sym: bool = False, dtype=np.float64, fma: bool = False):
     """MODWTTransform.inverse: pairwise in all three boundaries; SYMMETRIC reads t - l (``batch_sym``: t + l)."""
     dtype = np.dtype(dtype).type
     a = np.ascontiguousarray(np.asarray(approx), dtype=dtype)
@@ -167,7 +168,7 @@ def inverse1(approx, detail, lo, hi, boundary: int, batch_sym: bool = False, dty
         index = lambda t, off, n: (None, np.mod(t + off, n))
     else:
         index = lambda t, off, n: (None, _sym_index(t + off if batch_sym else t - off, n))
-    return _pairwise(a, d, flo, fhi, 1, index)
+    return _pairwise(a, d, flo, fhi, 1, index, fma)
 
 
 # ---- every upsampled tap, zeros included (VW_FLAG_REF_NONFINITE): slow scalar-order loops over l ----------------

@@ -4,7 +4,8 @@ Reference: tests/restatement_bi.py (pinned on the CPU by tests/test_restatement_
 their length patterns (analysis pair): bior1.1 (2,2), bior1.3 (6,2), bior2.2 (5,3), bior4.4 (9,7), bior3.9 (20,4),
 bior6.8 (17,16), rbio1.5 (2,10), rbio4.4 (7,9); the synthesis pair is the swap.
 
-Bars: EXACT bit-exact against the restatement.  FMA fp64 within 1e-12 * max(1, max|restatement|): the suite's
+Bars: EXACT bit-exact against the restatement.  FMA bit-exact against the restatement's FMA form (``fma=True``: each
+filter's own ``fma(x, f, acc)`` chain, the pairwise inverses ``acc + fma(lo, a, round(hi * d))``) and, as before, fp64 within 1e-12 * max(1, max|restatement|): the suite's
 1e-12 scaled by magnitude, because these banks are not normalised (the bound itself is at most (Llo + Lhi) * 2^-53
 of a level's largest magnitude per level, <= 2e-14 relative for J <= 4, L <= 20).  FMA fp32 within
 1e-5 * J * max(1, max|restatement|): the suite's fp32 bar (tests/test_gpu_f32_parity.py) scaled the same way.
@@ -72,6 +73,14 @@ def forward_ref(name, boundary, B, n, J, dt):
     return det, app
 
 
+@functools.lru_cache(maxsize=None)
+def forward_ref_fma(name, boundary, B, n, J, dt):
+    det, app = R.decompose(signals(B, n), *analysis(get_wavelet(name)), boundary, J, dtype=DTYPES[dt][0], fma=True)
+    det.setflags(write=False)
+    app.setflags(write=False)
+    return det, app
+
+
 def dev(a, dt="f64"):
     return torch.from_numpy(np.array(a, dtype=DTYPES[dt][0])).cuda()
 
@@ -127,6 +136,9 @@ def _transforms(engine, name, boundary):
             exact(app, a_ref, what + " approx")
             det_f, app_f = engine.forward(x, *analysis(w), WID_OTHER, boundary, J, nat.FLAG_FMA)
             tol = fma_tol(dt, J, d_ref, a_ref)
+            d_fma, a_fma = forward_ref_fma(name, boundary, B, n, J, dt)
+            exact(det_f, d_fma, what + " FMA details")
+            exact(app_f, a_fma, what + " FMA approx")
             close(det_f, d_ref, tol, what + " details")
             close(app_f, a_ref, tol, what + " approx")
             # inverse of the restatement's coefficients: plain, reconstructFromLevel / reconstructLevels masks,
@@ -141,6 +153,9 @@ def _transforms(engine, name, boundary):
                     continue
                 y_ref = R.reconstruct(d_ref, a_ref, *synthesis(w), boundary, WID_OTHER, mask, az, dtype=DTYPES[dt][0])
                 exact(engine.inverse(*args, 0, **kw), y_ref, f"{what} inverse mask={mask:b} az={az}")
+                y_fma = R.reconstruct(d_ref, a_ref, *synthesis(w), boundary, WID_OTHER, mask, az, dtype=DTYPES[dt][0],
+                                      fma=True)
+                exact(engine.inverse(*args, nat.FLAG_FMA, **kw), y_fma, f"{what} FMA inverse mask={mask:b} az={az}")
                 close(engine.inverse(*args, nat.FLAG_FMA, **kw), y_ref, fma_tol(dt, J, y_ref, d_ref, a_ref),
                       f"{what} inverse mask={mask:b} az={az}")
     torch.cuda.synchronize()
@@ -303,12 +318,16 @@ def _long_case(engine, name, boundary, B, n, J):
     exact(det, d_ref, "details")
     exact(app, a_ref, "approx")
     det_f, app_f = engine.forward(x, *analysis(w), WID_OTHER, boundary, J, nat.FLAG_FMA)
+    d_fma, a_fma = forward_ref_fma(name, boundary, B, n, J, "f64")
+    exact(det_f, d_fma, "FMA details")
+    exact(app_f, a_fma, "FMA approx")
     close(det_f, d_ref, fma_tol("f64", J, d_ref, a_ref), "details")
     close(app_f, a_ref, fma_tol("f64", J, d_ref, a_ref), "approx")
     y_ref = R.reconstruct(d_ref, a_ref, *synthesis(w), boundary)   # bior synthesis pairs: Lhi >= Llo (ZERO truncates)
     y = engine.inverse(det, app, *synthesis(w), WID_OTHER, boundary, J, 0)
     exact(y, y_ref, "inverse")
     y_f = engine.inverse(det, app, *synthesis(w), WID_OTHER, boundary, J, nat.FLAG_FMA)
+    exact(y_f, R.reconstruct(d_ref, a_ref, *synthesis(w), boundary, fma=True), "FMA inverse")
     close(y_f, y_ref, fma_tol("f64", J, y_ref, d_ref, a_ref), "inverse")
     torch.cuda.synchronize()
 
@@ -337,15 +356,23 @@ def test_single_level(engine, name, boundary):
         a, d = engine.forward1(dev(x), *analysis(w), boundary, 0)
         exact(a, a_ref, f"N={n} approx")
         exact(d, d_ref, f"N={n} detail")
+        a_fma, d_fma = R.forward1(x, *analysis(w), boundary, fma=True)
+        af, df = engine.forward1(dev(x), *analysis(w), boundary, nat.FLAG_FMA)
+        exact(af, a_fma, f"N={n} FMA approx")
+        exact(df, d_fma, f"N={n} FMA detail")
         if pairwise_throws(w):
             with pytest.raises(NotImplementedError, match="high-pass"):
                 engine.inverse1(a, d, *synthesis(w), boundary, 0)
             continue
         exact(engine.inverse1(a, d, *synthesis(w), boundary, 0), R.inverse1(a_ref, d_ref, *synthesis(w), boundary),
               f"N={n} inverse (high-pass truncated to {len(synthesis(w)[0])} taps)")
+        exact(engine.inverse1(a, d, *synthesis(w), boundary, nat.FLAG_FMA),
+              R.inverse1(a_ref, d_ref, *synthesis(w), boundary, fma=True), f"N={n} FMA inverse")
         if boundary == O.SYMMETRIC:
             exact(engine.inverse1(a, d, *synthesis(w), boundary, nat.FLAG_BATCH_SYM_INVERSE),
                   R.inverse1(a_ref, d_ref, *synthesis(w), boundary, batch_sym=True), f"N={n} batch inverse")
+            exact(engine.inverse1(a, d, *synthesis(w), boundary, nat.FLAG_BATCH_SYM_INVERSE | nat.FLAG_FMA),
+                  R.inverse1(a_ref, d_ref, *synthesis(w), boundary, batch_sym=True, fma=True), f"N={n} FMA batch inverse")
     torch.cuda.synchronize()
 
 

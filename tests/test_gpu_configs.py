@@ -10,7 +10,9 @@
   config 5  coif5 MODWT J=6 fp32, N = 8192 (no fp32 path in the reference: compared with the fp64
             restatement at a relative tolerance)
 
-Bar: bit-exact (max-abs 0) in EXACT mode, thresholds equal; FMA within 1e-12 * max|x| (north_star).
+Bar: bit-exact (max-abs 0) in EXACT mode, thresholds equal; FMA within 1e-12 * max|x| (north_star) and, for the
+config 4 and config 5 transforms, bit-exact against the restatement's FMA form on the rows picked
+(tests/restatement_generic.py ``fma=True``; the denoise chain of config 3 keeps its tolerance).
 """
 import math
 
@@ -20,6 +22,8 @@ import pytest
 from oracle import oracle as O
 import vectorwave_amd as vw
 from vectorwave_amd.wavelets import Coiflet, Daubechies, Haar, Symlet
+
+import restatement_generic as G
 
 pytestmark = pytest.mark.gpu
 
@@ -148,6 +152,14 @@ def test_config5_coif5_f32_j6_8192(engine):
     assert det.dtype == np.float32 and y.dtype == np.float32
     # SURVEY.md §8d fp32 bar: 1e-5 * max|x| * J (fp32 rounding through J levels of 30-tap sums)
     tol = 1e-5 * float(np.max(np.abs(x32))) * J
+    # FMA bits: the float32 FMA restatement (fmaf(x, f, acc) per tap) of the rows picked below, in one pass
+    rows = list(range(0, B, 9))
+    d_fma, a_fma = G.decompose(x32[rows], *lohi(w), O.PERIODIC, J, dtype=np.float32, fma=True)
+    y_fma = G.reconstruct(d_fma, a_fma, w.lowPassReconstruction(), w.highPassReconstruction(), O.PERIODIC, w.wavelet_id,
+                          dtype=np.float32, fma=True)
+    exact(det[:, rows, :], d_fma, "FMA details")
+    exact(app[rows], a_fma, "FMA approximation")
+    exact(y[rows], y_fma, "FMA inverse")
     for b in range(0, B, 9):
         xr = x32[b].astype(np.float64)
         d_ref, a_ref = O.decompose(xr, *lohi(w), O.PERIODIC, J)
@@ -226,6 +238,15 @@ def test_config4_full_batch_256x2p20(engine, fma):
     assert lib.vw_modwt_inverse_f64(engine.ctx, P(det), P(app), B, n, la, ha, len(lo), w.wavelet_id, nat.PERIODIC,
                                     J, 0xFFFFFFFF, 0, flags, P(y)) == 0, nat.last_error()
     torch.cuda.synchronize()
+    if fma:   # FMA bits: the restatement's fma(x, f, acc) chain on the three rows picked below, in one pass
+        rows = [0, B // 2 - 1, B - 1]
+        d_fma, a_fma = G.decompose(x[rows].cpu().numpy(), lo, hi, O.PERIODIC, J, fma=True)
+        y_fma = G.reconstruct(d_fma, a_fma, w.lowPassReconstruction(), w.highPassReconstruction(), O.PERIODIC,
+                              w.wavelet_id, fma=True)
+        exact(det[:, rows, :].cpu().numpy(), d_fma, "FMA details")
+        exact(app[rows].cpu().numpy(), a_fma, "FMA approximation")
+        exact(y[rows].cpu().numpy(), y_fma, "FMA inverse")
+        del d_fma, a_fma, y_fma
     for b in (0, B // 2 - 1, B - 1):
         xr = x[b].cpu().numpy()
         d_ref, a_ref = O.decompose(xr, lo, hi, O.PERIODIC, J, core=False)
@@ -266,6 +287,13 @@ def test_config5_full_batch_65536x8192_f32(engine):
     assert lib.vw_modwt_inverse_f32(engine.ctx, P(det), P(app), B, n, la, ha, len(lo), w.wavelet_id, nat.PERIODIC,
                                     J, 0xFFFFFFFF, 0, nat.FLAG_FMA, P(y)) == 0, nat.last_error()
     torch.cuda.synchronize()
+    rows = list(_full_rows(B))   # FMA bits: the float32 FMA restatement of the rows picked below
+    d_fma, a_fma = G.decompose(x[rows].cpu().numpy(), lo, hi, O.PERIODIC, J, dtype=np.float32, fma=True)
+    y_fma = G.reconstruct(d_fma, a_fma, w.lowPassReconstruction(), w.highPassReconstruction(), O.PERIODIC, w.wavelet_id,
+                          dtype=np.float32, fma=True)
+    exact(det[:, rows, :].cpu().numpy(), d_fma, "FMA details")
+    exact(app[rows].cpu().numpy(), a_fma, "FMA approximation")
+    exact(y[rows].cpu().numpy(), y_fma, "FMA inverse")
     for b in _full_rows(B):
         xr = x[b].double().cpu().numpy()
         tol = 1e-5 * float(np.max(np.abs(xr))) * J

@@ -2,7 +2,8 @@
 long signals past the multi-level tile group, one launch each way, streamed along the decimated
 coordinate with per-level LDS rings.  EXACT: bit-exact against the restatement of vectorwave-core
 (MultiLevelMODWTTransform.java:243-251 forward, :339-349 / :576-589 inverse); FMA: identical bits to
-the column sweeps they replace (same per-output operation sequence, VW_DEEP=0 A/B).  Shapes cover
+the column sweeps they replace (same per-output operation sequence, VW_DEEP=0 A/B) and to the restatement's FMA
+form (tests/restatement_generic.py ``fma=True``: one fma(x, f, acc) per tap).  Shapes cover
 several groups / segments, residue blocks, fp32 (C = 16), masked details, zero approximation, the
 fused denoise thresholds, and an N the deep path must decline (N % P != 0)."""
 import numpy as np
@@ -12,6 +13,8 @@ from oracle import oracle as O
 import vectorwave_amd as vw
 from vectorwave_amd import _native as nat
 from vectorwave_amd.wavelets import Coiflet, Daubechies, Haar, Symlet
+
+import restatement_generic as G
 
 pytestmark = pytest.mark.gpu
 
@@ -69,6 +72,27 @@ def test_deep_matches_column_sweeps(engine, w, n, J, dt):
         torch.cuda.synchronize()
         assert torch.equal(d1, d0) and torch.equal(a1, a0), (w.name(), dt, flags)
         assert torch.equal(y1, y0), (w.name(), dt, flags)
+
+
+@pytest.mark.parametrize("w,n,J,B,dt", [(Haar.INSTANCE, 1 << 13, 12, 3, "f64"), (Daubechies.DB4, 1 << 14, 10, 2, "f64"),
+                                        (Coiflet.COIF5, 1 << 15, 8, 1, "f32")],
+                         ids=["haar-2^13-J12-f64", "db4-2^14-J10-f64", "coif5-2^15-J8-f32"])
+def test_deep_fma_bit_exact_against_the_fma_restatement(engine, w, n, J, B, dt):
+    """The FMA run of the deep path at the smallest shapes this file runs it on, per element type: forward, and the
+    inverse of the forward's planes, against the FMA restatement of the same type."""
+    import torch
+    npdt, tdt = (np.float64, torch.float64) if dt == "f64" else (np.float32, torch.float32)
+    xh = _rows(B, n, 5).astype(npdt)
+    x = torch.from_numpy(xh).cuda()
+    d, a = engine.forward(x, *lohi(w), w.wavelet_id, O.PERIODIC, J, nat.FLAG_FMA)
+    y = engine.inverse(d, a, *lohi_r(w), w.wavelet_id, O.PERIODIC, J, nat.FLAG_FMA)
+    torch.cuda.synchronize()
+    assert d.dtype == tdt
+    d_ref, a_ref = G.decompose(xh, *lohi(w), O.PERIODIC, J, dtype=npdt, fma=True)
+    y_ref = G.reconstruct(d_ref, a_ref, *lohi_r(w), O.PERIODIC, w.wavelet_id, dtype=npdt, fma=True)
+    assert np.array_equal(d.cpu().numpy(), d_ref), "details"
+    assert np.array_equal(a.cpu().numpy(), a_ref), "approx"
+    assert np.array_equal(y.cpu().numpy(), y_ref), "inverse"
 
 
 @pytest.mark.parametrize("lds", [40, 160])

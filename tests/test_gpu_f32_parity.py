@@ -6,7 +6,9 @@ are ``float(h * (1 / sqrt 2))`` rounded once.  tests/restatement_generic.py is t
 (bit-equal to the C restatement at float64: tests/test_restatement_generic_cpu.py), so:
 
   EXACT fp32 == the float32 restatement bit for bit, and within 1e-5 * max|x| * J of the fp64 restatement;
-  FMA fp32 within that bar, and bit-equal across kernel policies.
+  FMA fp32 == the float32 restatement with ``fma=True`` bit for bit (``fmaf(x, f, acc)`` per tap, the ZERO_PADDING
+  inverse ``acc + fmaf(lo, a, round(hi * d))``: the correctly rounded primitive, tests/test_restatement_fma_cpu.py),
+  within that bar as well, and bit-equal across kernel policies.
 
 fp32 vectors hold 4 elements (fp64: 2): the shapes cover every N mod 4, row tails of 1..3 elements, halos rounded to
 4, SYMMETRIC shifts that are no multiple of 4, leading dimensions that break the row alignment, and host memory.
@@ -50,7 +52,8 @@ def inputs(B, n, seed=5):
 
 @functools.lru_cache(maxsize=None)
 def reference(name, boundary, B, n, J, mask=None, approx_zero=False):
-    """float32 restatement (d, a, y) and fp64 restatement (d, a, y) of the same float32 input, computed once."""
+    """float32 restatement (d, a, y), fp64 restatement (d, a, y) and float32 FMA restatement (d, a, y, y of the EXACT
+    planes) of the same float32 input, computed once."""
     w = ALL[name]
     x = inputs(B, n)
     m = (1 << J) - 1 if mask is None else mask
@@ -61,8 +64,12 @@ def reference(name, boundary, B, n, J, mask=None, approx_zero=False):
         d64[:, b, :], a64[b] = O.decompose(x[b].astype(np.float64), *lohi(w), boundary, J, core=boundary != O.PERIODIC)
         y64[b] = O.reconstruct(d64[:, b, :], a64[b], *lohi(w), boundary, w.wavelet_id, detail_mask=m,
                                approx_zero=approx_zero)
-    out = (d32, a32, y32, d64, a64, y64)
-    for a in out:
+    df, af = G.decompose(x, *lohi(w), boundary, J, dtype=F32, fma=True)
+    kw = dict(detail_mask=m, approx_zero=approx_zero, dtype=F32, fma=True)
+    yf = G.reconstruct(df, af, *lohi(w), boundary, w.wavelet_id, **kw)
+    yf32 = G.reconstruct(d32, a32, *lohi(w), boundary, w.wavelet_id, **kw)   # the FMA inverse of the EXACT planes
+    out = (d32, a32, y32, d64, a64, y64, (df, af, yf, yf32))
+    for a in out[:6] + out[6]:
         a.setflags(write=False)
     return out
 
@@ -102,7 +109,7 @@ def run(engine, w, x, boundary, J, flags, d_in=None, a_in=None, mask=0xFFFFFFFF,
 
 
 def check_policies(engine, w, boundary, B, n, J, policies):
-    d32, a32, y32, d64, a64, y64 = reference(w.name(), boundary, B, n, J)
+    d32, a32, y32, d64, a64, y64, (df, af, yf, _) = reference(w.name(), boundary, B, n, J)
     x = torch.from_numpy(np.array(inputs(B, n))).cuda()
     tol = tol_of(inputs(B, n), J)
     for flags in (0, nat.FLAG_FMA):
@@ -119,6 +126,10 @@ def check_policies(engine, w, boundary, B, n, J, policies):
             exact(det, d32)
             exact(app, a32)
             exact(y, y32)
+        else:
+            exact(det, df)
+            exact(app, af)
+            exact(y, yf)
         within(det, d64, tol)
         within(app, a64, tol)
         within(y, y64, tol)
@@ -155,13 +166,14 @@ def test_partial_reconstruction(engine, w, boundary, tiled, n):
     tol = tol_of(inputs(B, n), J)
     for mask in (0b110, 0b001):
         for az in (False, True):
-            d32, a32, y32, d64, a64, y64 = reference(w.name(), boundary, B, n, J, mask, az)
+            d32, a32, y32, d64, a64, y64, (_, _, _, yf32) = reference(w.name(), boundary, B, n, J, mask, az)
             d, a = torch.from_numpy(np.array(d32)).cuda(), torch.from_numpy(np.array(a32)).cuda()
             with engine.options(VW_FORCE_TILED=tiled):
                 ys = [engine.inverse(d, None if az else a, *lohi(w), w.wavelet_id, boundary, J, flags, detail_mask=mask,
                                      approx_zero=az, shape=(B, n)) for flags in (0, nat.FLAG_FMA)]
             torch.cuda.synchronize()
             exact(ys[0], y32)
+            exact(ys[1], yf32)
             for y in ys:
                 within(y, y64, tol)
 
@@ -200,6 +212,10 @@ def test_forward_leading_dimension(engine, dt, pad):
             else:
                 exact(det, d64)
                 exact(app, a64)
+        else:
+            df, af = G.decompose(xh, *lohi(w), O.PERIODIC, J, dtype=F32 if dt == "f32" else np.float64, fma=True)
+            exact(det, df)
+            exact(app, af)
         within(det, d64, tol)
         within(app, a64, tol)
 
@@ -210,7 +226,7 @@ def test_forward_leading_dimension(engine, dt, pad):
 def test_host_memory(engine, boundary, n):
     """numpy float32 in and out: the staged host path of the fp32 entry points."""
     w, B, J = Symlet.SYM8, 3, 4
-    d32, a32, y32, d64, a64, y64 = reference(w.name(), boundary, B, n, J)
+    d32, a32, y32, d64, a64, y64, (df, af, yf, _) = reference(w.name(), boundary, B, n, J)
     x = np.array(inputs(B, n))
     det, app, y = run(engine, w, x, boundary, J, 0)
     assert isinstance(det, np.ndarray) and det.dtype == F32 and y.dtype == F32
@@ -218,6 +234,9 @@ def test_host_memory(engine, boundary, n):
     exact(app, a32)
     exact(y, y32)
     det, app, y = run(engine, w, x, boundary, J, nat.FLAG_FMA)
+    exact(det, df)
+    exact(app, af)
+    exact(y, yf)
     tol = tol_of(x, J)
     within(det, d64, tol)
     within(app, a64, tol)

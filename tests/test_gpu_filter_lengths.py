@@ -5,7 +5,9 @@ Here: the listed-but-untested lengths (sym5 10, sym7 14, db10 20, coif4 24) and 
 run the runtime-L kernels -- even 22, 28, 32, 60, 64 (the ABI's limit) and odd 3, 9, 31, as synthetic banks
 (tests/restatement_generic.synthetic_filter: pseudo-random taps with sum|lo| = sqrt(2), QMF high-pass, VW_WID_OTHER).
 
-Bars (the suite's own): EXACT bit-exact against the CPU restatement; FMA within 1e-12 (|x| <= 1 and a gain of at
+Bars (the suite's own): EXACT bit-exact against the CPU restatement; FMA bit-exact against the restatement's FMA
+form (tests/restatement_generic.py ``fma=True``: ``fma(x, f, acc)`` per tap, the ZERO_PADDING inverse
+``acc + fma(lo, a, round(hi * d))``), within 1e-12 of the EXACT one (|x| <= 1 and a gain of at
 most 1 per level: at most L * 2^-53 * max|x| per level, below 3e-14 over the J <= 5 levels here) and bit-equal
 between kernel policies.  PERIODIC references use the batch semantics (core=False: no FFT region); calls go to the
 engine without validation flags, on device tensors, so the persistent / register-blocked choices are reachable.
@@ -23,6 +25,7 @@ from vectorwave_amd import _native as nat
 from vectorwave_amd.errors import VW_ERR_ARG
 from vectorwave_amd.wavelets import WID_OTHER, Coiflet, Daubechies, Symlet, Wavelet
 
+import restatement_bi as RB
 import restatement_generic as G
 
 pytestmark = pytest.mark.gpu
@@ -72,6 +75,21 @@ def reference(name, boundary, B, n, J, mask=None, approx_zero=False):
     return det, app, y
 
 
+@functools.lru_cache(maxsize=None)
+def reference_fma(name, boundary, B, n, J, mask=None, approx_zero=False):
+    """The FMA restatement: (details, approx) of the signals, y of those planes, and y of the EXACT reference's planes
+    (what the tests that feed the inverse the reference's coefficients get); computed once per case and shared."""
+    w = next(f for f in FILTERS if f.name() == name)
+    d_ref, a_ref, _ = reference(name, boundary, B, n, J, mask, approx_zero)
+    kw = dict(detail_mask=(1 << J) - 1 if mask is None else mask, approx_zero=approx_zero, fma=True)
+    det, app = G.decompose(signals(B, n), *lohi(w), boundary, J, fma=True)
+    y_own = G.reconstruct(det, app, *lohi(w), boundary, w.wavelet_id, **kw)
+    y_of_ref = G.reconstruct(d_ref, a_ref, *lohi(w), boundary, w.wavelet_id, **kw)
+    for a in (det, app, y_own, y_of_ref):
+        a.setflags(write=False)
+    return det, app, y_own, y_of_ref
+
+
 def exact(a, b):
     a = a.cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)
     b = b.cpu().numpy() if isinstance(b, torch.Tensor) else np.asarray(b)
@@ -97,7 +115,8 @@ def round_trip(engine, w, x, boundary, J, flags, mask=0xFFFFFFFF, approx_zero=Fa
 
 
 def check_both_modes(engine, w, boundary, B, n, J):
-    """EXACT bit-exact (forward, inverse of the forward's outputs == inverse of the reference's); FMA within 1e-12."""
+    """EXACT bit-exact (forward, inverse of the forward's outputs == inverse of the reference's); FMA bit-exact
+    against the FMA restatement (forward; inverse of the EXACT reference's planes) and within 1e-12."""
     d_ref, a_ref, y_ref = reference(w.name(), boundary, B, n, J)
     x = torch.from_numpy(np.array(signals(B, n))).cuda()
     det, app, y = round_trip(engine, w, x, boundary, J, 0)
@@ -106,6 +125,10 @@ def check_both_modes(engine, w, boundary, B, n, J):
     exact(y, y_ref)
     det, app, y = round_trip(engine, w, x, boundary, J, nat.FLAG_FMA,
                              det_app=(torch.from_numpy(np.array(d_ref)).cuda(), torch.from_numpy(np.array(a_ref)).cuda()))
+    d_fma, a_fma, _, y_fma = reference_fma(w.name(), boundary, B, n, J)
+    exact(det, d_fma)
+    exact(app, a_fma)
+    exact(y, y_fma)
     close(det, d_ref)
     close(app, a_ref)
     close(y, y_ref)
@@ -139,6 +162,10 @@ def test_kernel_policies_periodic(engine, w, B, n):
                 assert torch.equal(t0, t1), (opts, "fma" if flags else "exact")
         det, app, y = outs[0]
         if flags:
+            d_fma, a_fma, y_fma, _ = reference_fma(w.name(), O.PERIODIC, B, n, J)
+            exact(det, d_fma)
+            exact(app, a_fma)
+            exact(y, y_fma)
             close(det, d_ref)
             close(app, a_ref)
         else:
@@ -162,6 +189,10 @@ def test_nv8_blocked_forward(engine, L):
             assert torch.equal(t0, t1), "fma" if flags else "exact"
         det, app, y = outs[1]
         if flags:
+            d_fma, a_fma, y_fma, _ = reference_fma(w.name(), O.PERIODIC, B, n, J)
+            exact(det, d_fma)
+            exact(app, a_fma)
+            exact(y, y_fma)
             close(det, d_ref)
             close(app, a_ref)
         else:
@@ -212,6 +243,7 @@ def test_partial_reconstruction(engine, L, boundary, tiled):
                                     detail_mask=mask, approx_zero=az, shape=(B, n))
             torch.cuda.synchronize()
             exact(y, y_ref)
+            exact(yf, reference_fma(w.name(), boundary, B, n, J, mask, az)[3])
             close(yf, y_ref)
 
 
@@ -256,6 +288,16 @@ def test_single_level(engine, L, boundary, n):
     for b in range(4):
         a_ref, d_ref = O.modwt_forward(x[b], *lohi(w), boundary)
         exact(ys[b], O.modwt_inverse(a_ref, d_ref, *lohi(w), boundary, batch_optimized=n >= 64))
+    # FMA: fma(x, f, acc) per forward tap, the pairwise inverse acc + fma(lo, a, round(hi * d)) in every boundary
+    txf = vw.MODWTTransform(w, vw.BoundaryMode(boundary), fma=True)
+    rf = txf.forwardBatch(x)
+    a_fma, d_fma = RB.forward1(x, *lohi(w), boundary, fma=True)
+    ysf = txf.inverseBatch(rf)
+    for b in range(4):
+        exact(rf[b].approximationCoeffs(), a_fma[b])
+        exact(rf[b].detailCoeffs(), d_fma[b])
+        exact(txf.inverse(rf[b]), RB.inverse1(a_fma[b], d_fma[b], *lohi(w), boundary, fma=True))
+        exact(ysf[b], RB.inverse1(a_fma[b], d_fma[b], *lohi(w), boundary, batch_sym=n >= 64, fma=True))
 
 
 # ---- 8. SWT denoise ----------------------------------------------------------------------------------------------------

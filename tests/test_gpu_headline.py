@@ -8,7 +8,9 @@ persistent workgroup, b and b + 1 by neighbours on different CUs / XCDs.
 
 Bars: FMA (the bench's accumulation) within 1e-12 of the restatement of vectorwave-core
 (MultiLevelMODWTTransform.java:243-251 forward, :339-349 / :576-589 inverse) for details, approximation
-and the reconstruction; EXACT bit-exact for forward AND inverse rows.
+and the reconstruction, and bit-exact against the restatement's FMA form (tests/restatement_generic.py
+``fma=True``: one ``fma(x, f, acc)`` per tap, pinned on the CPU by tests/test_restatement_fma_cpu.py); EXACT
+bit-exact for forward AND inverse rows.
 """
 import numpy as np
 import pytest
@@ -16,6 +18,8 @@ import pytest
 from oracle import oracle as O
 from vectorwave_amd import _native as nat
 from vectorwave_amd.wavelets import Daubechies
+
+import restatement_generic as G
 
 pytestmark = pytest.mark.gpu
 
@@ -51,10 +55,22 @@ def _oracle(xrow):
     return d, a, y
 
 
+def _fma_restatement(xrows):
+    w = Daubechies.DB4
+    d, a = G.decompose(xrows, w.lowPassDecomposition(), w.highPassDecomposition(), O.PERIODIC, J, fma=True)
+    y = G.reconstruct(d, a, w.lowPassReconstruction(), w.highPassReconstruction(), O.PERIODIC, w.wavelet_id, fma=True)
+    return d, a, y
+
+
 def test_headline_fma_rows_within_1e12(engine, headline):
     det, app, y = _run(engine, headline, nat.FLAG_FMA)
     w = Daubechies.DB4
     worst = 0.0
+    d_fma, a_fma, y_fma = _fma_restatement(headline[list(ROWS)].cpu().numpy())   # the eleven rows in one pass
+    for i, b in enumerate(ROWS):
+        assert np.array_equal(det[:, b, :].cpu().numpy(), d_fma[:, i, :]), f"FMA forward row {b}: not the restatement's bits"
+        assert np.array_equal(app[b].cpu().numpy(), a_fma[i]), f"FMA approx row {b}: not the restatement's bits"
+        assert np.array_equal(y[b].cpu().numpy(), y_fma[i]), f"FMA inverse row {b}: not the restatement's bits"
     for b in ROWS:
         xr = headline[b].cpu().numpy()
         d_ref, a_ref, y_ref = _oracle(xr)
@@ -65,6 +81,9 @@ def test_headline_fma_rows_within_1e12(engine, headline):
         # the inverse alone, on the kernel's own FMA coefficients
         y_own = O.reconstruct(gd, ga, w.lowPassReconstruction(), w.highPassReconstruction(), O.PERIODIC)
         np.testing.assert_allclose(gy, y_own, rtol=0, atol=TOL)
+        y_own_fma = G.reconstruct(gd, ga, w.lowPassReconstruction(), w.highPassReconstruction(), O.PERIODIC,
+                                  w.wavelet_id, fma=True)
+        assert np.array_equal(gy, y_own_fma), f"FMA inverse of the kernel's own coefficients, row {b}"
         worst = max(worst, float(np.max(np.abs(gy - y_ref))), float(np.max(np.abs(gd - d_ref))))
     assert worst < TOL
     # whole batch: perfect reconstruction of the truncated db4 taps (SURVEY.md key fact 5)

@@ -9,7 +9,10 @@ bit, signs of zeros included.
 
 Tolerances of the FMA runs are the existing inverse tests': fp64 max-abs < 1e-12 on unit-scale planes
 (tests/test_gpu_headline.py), fp32 1e-5 * max|planes| * J against the fp64 restatement
-(tests/test_gpu_f32_parity.py tol_of).
+(tests/test_gpu_f32_parity.py tol_of).  Beside them the FMA runs are compared bit for bit with the FMA restatement
+of the path that ran: k_mra's branch passes (mra_restatement.mra, ``fma=True``) or the loop path's masked inverses
+(mra_restatement.mra_by_masks, ``fma=True``) -- the same bytes for PERIODIC and SYMMETRIC, two different fixed
+sequences for ZERO_PADDING, whose masked pairwise term rounds the single product before adding it.
 """
 import functools
 from ctypes import c_void_p
@@ -17,6 +20,7 @@ from ctypes import c_void_p
 import numpy as np
 import pytest
 
+import mra_restatement as M
 import restatement_generic as G
 from oracle import oracle as O
 import vectorwave_amd as vw
@@ -100,6 +104,19 @@ def _reference(fname, bname, N, J, dname):
     return ref
 
 
+@functools.lru_cache(maxsize=None)
+def _reference_fma(fname, bname, N, J, dname):
+    """(k_mra's sequence, the loop path's sequence), each [J+1, 5, N] in the element type, FMA mode."""
+    lo, hi, wid = _filter(fname)
+    dt = DTYPES[dname]
+    det, app = _planes(N, J)
+    out = (M.mra(det.astype(dt), app.astype(dt), lo, hi, BOUNDS[bname], wid, dtype=dt, fma=True),
+           M.mra_by_masks(det.astype(dt), app.astype(dt), lo, hi, BOUNDS[bname], wid, dtype=dt, fma=True))
+    for a in out:
+        a.setflags(write=False)
+    return out
+
+
 def _oracle_rows(fname, bname, N, J, rows):
     """{row: [J+1, N]} from the C restatement (fp64)."""
     lo, hi, wid = _filter(fname)
@@ -159,6 +176,42 @@ def test_exact_components_bit_equal(engine, fname, bname, dname):
 
 
 # ---- 2. FMA ------------------------------------------------------------------------------------------
+def _fused_ran(engine, fn):
+    """(fn's result, whether k_mra ran): the timing families count the launches, as test_paths_are_the_planned_ones."""
+    engine.reset_timing()
+    engine.enable_timing(True)
+    try:
+        out = fn()
+        engine.synchronize()
+        mra_n, inv_n = engine.kernel_time("mra")[1], engine.kernel_time("inverse")[1] + engine.kernel_time("inverse_level")[1]
+    finally:
+        engine.enable_timing(False)
+        engine.reset_timing()
+    assert (mra_n > 0) != (inv_n > 0), (mra_n, inv_n)
+    return out, mra_n > 0
+
+
+def _check_fma_bits(engine, default_out, fname, bname, N, J, dname):
+    """The default call, k_mra forced (VW_MRA_FUSED=2) and the loop path (VW_MRA_FUSED=0), each against the FMA
+    restatement of the path that ran."""
+    fused_ref, loop_ref = _reference_fma(fname, bname, N, J, dname)
+    if bname != "Z":
+        assert _same_bits(fused_ref, loop_ref), ("the two FMA sequences", fname, bname, N, J, dname)
+    paths = []
+    for mode in (-1, 2, 0):
+        with engine.options(VW_MRA_FUSED=mode):
+            got, fused = _fused_ran(engine, lambda: _run_planes(engine, fname, bname, N, J, MAXB, dname, nat.FLAG_FMA))
+        assert _same_bits(got, fused_ref if fused else loop_ref), \
+            (f"fma bits {fname} {bname} N={N} J={J} {dname} VW_MRA_FUSED={mode} k_mra ran={fused}: "
+             f"{int(np.count_nonzero(got != fused_ref))} outputs differ from k_mra's sequence, "
+             f"{int(np.count_nonzero(got != loop_ref))} from the loop path's")
+        if mode == -1:
+            assert _same_bits(got, default_out), ("timing changed the bits", fname, bname, N, J, dname)
+        paths.append(fused)
+    assert not paths[2], "VW_MRA_FUSED=0 ran k_mra"
+    return paths
+
+
 @pytest.mark.parametrize("dname", list(DTYPES))
 @pytest.mark.parametrize("bname", list(BOUNDS))
 @pytest.mark.parametrize("fname", FILTERS)
@@ -170,7 +223,9 @@ def test_fma_within_the_inverse_bars(engine, fname, bname, dname):
         for J in sorted({1, 3, max(_largest(L, N), 1)}):
             if not _fits(L, J, N):
                 continue
-            got = _run_planes(engine, fname, bname, N, J, MAXB, dname, nat.FLAG_FMA).astype(np.float64)
+            raw = _run_planes(engine, fname, bname, N, J, MAXB, dname, nat.FLAG_FMA)
+            _check_fma_bits(engine, raw, fname, bname, N, J, dname)
+            got = raw.astype(np.float64)
             ref = np.asarray(_reference(fname, bname, N, J, "f64"))
             det, app = _planes(N, J)
             tol = 1e-12 if dname == "f64" else 1e-5 * max(np.max(np.abs(det)), np.max(np.abs(app))) * J

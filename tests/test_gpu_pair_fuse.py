@@ -4,7 +4,8 @@ The round-trip kernel (vw_pair.hip) runs the persistent forward's loop body and 
 the same row, keeping a_J and d_J in registers and reading d_{J-1} .. d_1 back right after storing them.  Per
 output the operation sequence is that of the two separate kernels, so with the switch on and off -- two contexts,
 the way tests/test_gpu_inverse_waves.py switches VW_INV_WAVES -- details, approx and y are the same BYTES, EXACT is
-bit-exact against the restatement, and vw_graph_stats says what the capture recorded: K fused pairs, or none.
+bit-exact against the restatement, FMA bit-exact against the restatement's FMA form (tests/restatement_generic.py
+``fma=True``), and vw_graph_stats says what the capture recorded: K fused pairs, or none.
 
 Shapes are the smallest at which each mechanism can go wrong: N = 512 (one wave per workgroup; at deep levels the
 right halo spans more than the first slab, so it is copied after a barrier), N = 1024, N = 4096 (8 waves); J = 1 (no
@@ -21,6 +22,8 @@ from oracle import oracle as O
 import vectorwave_amd as vw
 from vectorwave_amd import _native as nat
 from vectorwave_amd.wavelets import Daubechies, Haar, Symlet
+
+import restatement_generic as G
 
 pytestmark = pytest.mark.gpu
 
@@ -166,6 +169,24 @@ def test_exact_is_bit_exact_against_the_restatement(pair, w):
         assert np.array_equal(det[0][:, b, :], d_ref), f"details row {b}"
         assert np.array_equal(app[0][b], a_ref), f"approx row {b}"
         assert np.array_equal(y[0][b], O.reconstruct(d_ref, a_ref, *rlohi(w), O.PERIODIC, w.wavelet_id)), f"y row {b}"
+
+
+@pytest.mark.parametrize("w", WAVELETS, ids=lambda w: w.name())
+def test_fma_is_bit_exact_against_the_fma_restatement(pair, w):
+    """The FMA twin, at every N of this file: the captured round trip equals reconstruct(decompose(x, fma), fma) --
+    one fma(x, f, acc) per tap -- at the row's deepest level, three rows.  Every other FMA variant here is tied to
+    this one by the "same bytes" tests."""
+    on, _ = pair
+    for N in (512, 1024, 4096):
+        J = vw.max_levels(N, len(lohi(w)[0]))
+        (det, app, y), (_, fused) = run(on, Case(w, 3, N, J, nat.FLAG_FMA, steps=1))
+        assert fused == 1
+        x = O.fill_uniform(3 * N, 7).reshape(3, N)
+        d_ref, a_ref = G.decompose(x, *lohi(w), O.PERIODIC, J, fma=True)
+        y_ref = G.reconstruct(d_ref, a_ref, *rlohi(w), O.PERIODIC, w.wavelet_id, fma=True)
+        assert np.array_equal(det[0], d_ref), f"N={N} details"
+        assert np.array_equal(app[0], a_ref), f"N={N} approx"
+        assert np.array_equal(y[0], y_ref), f"N={N} y"
 
 
 @pytest.mark.parametrize("J,flags", [(2, nat.FLAG_FMA), (3, 0)], ids=["J2-fma", "J3-exact"])

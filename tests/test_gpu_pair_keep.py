@@ -22,6 +22,8 @@ import vectorwave_amd as vw
 from vectorwave_amd import _native as nat
 from vectorwave_amd.wavelets import Daubechies, Haar, Symlet
 
+import restatement_generic as G
+
 pytestmark = pytest.mark.gpu
 
 K = 2  # forward -> inverse pairs per capture
@@ -197,6 +199,22 @@ def test_exact_keep2_is_bit_exact_against_the_restatement(ctxs, w):
         assert np.array_equal(det[0][:, b, :], d_ref), f"details row {b}"
         assert np.array_equal(app[0][b], a_ref), f"approx row {b}"
         assert np.array_equal(y[0][b], O.reconstruct(d_ref, a_ref, *rlohi(w), O.PERIODIC, w.wavelet_id)), f"y row {b}"
+
+
+@pytest.mark.parametrize("w,N", CASES, ids=lambda v: v.name() if hasattr(v, "name") else str(v))
+def test_fma_keep2_is_bit_exact_against_the_fma_restatement(ctxs, w, N):
+    """The FMA twin: KEEP = 2 at the row's deepest level, three rows, against reconstruct(decompose(x, fma), fma) of
+    tests/restatement_generic.py (one fma(x, f, acc) per tap).  KEEP = 0 / 1 and the two separate kernels are tied to
+    it by test_every_variant_gives_the_unfused_bytes."""
+    L = len(lohi(w)[0])
+    J = vw.max_levels(N, L)
+    (det, app, y), fused = run(forced(ctxs, 2, N, L, J, nat.FLAG_FMA), w, 3, N, J, nat.FLAG_FMA, steps=1)
+    assert fused == 1
+    x = O.fill_uniform(3 * N, 7).reshape(3, N)
+    d_ref, a_ref = G.decompose(x, *lohi(w), O.PERIODIC, J, fma=True)
+    assert np.array_equal(det[0], d_ref), "details"
+    assert np.array_equal(app[0], a_ref), "approx"
+    assert np.array_equal(y[0], G.reconstruct(d_ref, a_ref, *rlohi(w), O.PERIODIC, w.wavelet_id, fma=True)), "y"
 
 
 @pytest.mark.parametrize("N", [512, 1024, 4096])
