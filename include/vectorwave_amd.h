@@ -154,6 +154,17 @@ enum {
     VW_FLAG_TREE_SUMS = 1u << 9
 };
 
+/* ---- arrays: alignment, leading dimensions, extents ----------------------
+ * Every array argument needs only the alignment of its element type (8 bytes for double, 4 for float): a pointer
+ * into the middle of a larger buffer is fine, e.g. an element offset into a Java primitive array.  The engine uses
+ * 16-byte vector loads and stores where every array of a launch happens to be 16-byte aligned and the rows are whole
+ * vectors, and element accesses otherwise; the results are the same bits either way.  Row inputs take any leading
+ * dimension ldx >= N and are (B - 1) * ldx + N elements long: the last row has no padding.  Bytes outside
+ * [row, row + N) of an input -- row padding, whatever precedes or follows the array -- are neither read into any
+ * result nor checked by VW_FLAG_VALIDATE or VW_FLAG_REF_NONFINITE; they may hold anything, NaN included.  Inputs are
+ * never written.  Outputs are written exactly over their documented extent, every element of it, and nothing
+ * outside it (tests/test_gpu_footprint.py). */
+
 /* ---- context ---------------------------------------------------------- */
 VW_API vw_status vw_ctx_create(int device, vw_ctx **out);
 VW_API vw_status vw_ctx_destroy(vw_ctx *ctx);

@@ -26,11 +26,13 @@ struct Case {
   long long N;
   int Llo, Lhi, J, boundary;
   unsigned flags;
+  int off = 0;  // mask of the caller pointers one element off a 16-byte boundary: forward 1 x, 2 details, 4 approx;
+                // inverse 1 details, 2 approx, 4 y
 };
 static void finding(const Case& c, const char* rule, long long a = 0, long long b = 0) {
   if (++g_findings > 100) return;
-  printf("%s %s N=%lld Llo=%d Lhi=%d J=%d boundary=%d flags=0x%x [%s] | %s (%lld, %lld)\n", c.dir, c.dtype, c.N, c.Llo,
-         c.Lhi, c.J, c.boundary, c.flags, c.tune, rule, a, b);
+  printf("%s %s N=%lld Llo=%d Lhi=%d J=%d boundary=%d flags=0x%x off=%d [%s] | %s (%lld, %lld)\n", c.dir, c.dtype, c.N, c.Llo,
+         c.Lhi, c.J, c.boundary, c.flags, c.off, c.tune, rule, a, b);
 }
 
 // the tap count a bank of two lengths runs: the longer filter's, or one more where only that count is listed
@@ -80,7 +82,7 @@ static void forward_case(const Tuning& tu, Case c) {
   c.dir = "fwd";
   alignas(16) static T dummy[4];
   FwdCall<T> k;
-  k.x = dummy; k.details = dummy; k.approx = dummy;   // aligned, never dereferenced by the planner
+  k.x = dummy + (c.off & 1); k.details = dummy + ((c.off >> 1) & 1); k.approx = dummy + ((c.off >> 2) & 1);  // never dereferenced by the planner
   k.B = 3; k.N = c.N; k.ldx = c.N; k.L = c.Llo; k.Lhi = c.Lhi; k.boundary = c.boundary; k.J = c.J; k.flags = c.flags;
   FwdPlan<T> p;
   plan_forward(tu, k, &p);
@@ -101,6 +103,8 @@ static void forward_case(const Tuning& tu, Case c) {
     return;
   }
   if (p.error != VW_OK) return finding(c, "unexpected plan error", p.error);
+  // the fused kernels read x and write the details and the approximation at row + w * V: no vector form off alignment
+  if (c.off && p.fused && (p.args.vec_io || p.args.unrolled)) finding(c, "vector I/O on a misaligned pointer", c.off);
   // the two-length route (VW_BI bit 0): the non-persistent fused forward at each filter's own count, halos for the longer
   const bool bi_route = p.args.taps_hi != p.args.taps;
   if (bi_route) {
@@ -108,7 +112,7 @@ static void forward_case(const Tuning& tu, Case c) {
       finding(c, "two-length route outside its kernel", p.kernel, p.nv);
     if (p.args.taps != c.Llo || p.args.taps_hi != c.Lhi) finding(c, "two-length route tap counts", p.args.taps, p.args.taps_hi);
     if (p.args.unrolled && !has_unrolled_pair(c.Llo, c.Lhi)) finding(c, "unrolled two-length kernel at an unlisted pair");
-    if (!(tu.bi & 4) && !p.args.unrolled) finding(c, "runtime-L two-length forward without VW_BI bit 2");
+    if (!(tu.bi & 4) && !p.args.unrolled && !c.off) finding(c, "runtime-L two-length forward without VW_BI bit 2");
     Lmax = std::max(c.Llo, c.Lhi);
   } else {
     if ((tu.bi & 1) && (tu.bi & 4) && c.Llo != c.Lhi && p.fused) finding(c, "padded route where the two-length forward fits", p.kernel);
@@ -145,7 +149,7 @@ static void inverse_case(const Tuning& tu, Case c, bool single) {
   c.dir = single ? "inv1" : "inv";
   alignas(16) static T dummy[4];
   InvCall<T> k;
-  k.details = dummy; k.approx = dummy; k.y = dummy;
+  k.details = dummy + (c.off & 1); k.approx = dummy + ((c.off >> 1) & 1); k.y = dummy + ((c.off >> 2) & 1);
   k.B = 3; k.N = c.N; k.L = c.Llo; k.Lhi = c.Lhi; k.boundary = c.boundary; k.J = single ? 1 : c.J; k.flags = c.flags;
   k.single_level = single;
   if (single) k.detail_mask = 1u;
@@ -157,6 +161,7 @@ static void inverse_case(const Tuning& tu, Case c, bool single) {
     return;
   }
   if (p.error != VW_OK) return finding(c, "unexpected plan error", p.error);
+  if (c.off && p.fused && (p.args.vec_io || p.args.unrolled || p.args.full)) finding(c, "vector I/O on a misaligned pointer", c.off);
   // the two-length route (VW_BI): the fused sequential-sum kernels, each branch at its own count, halos for the longer
   const bool bi_route = p.args.taps_hi != p.args.taps;
   if (bi_route) {
@@ -164,7 +169,7 @@ static void inverse_case(const Tuning& tu, Case c, bool single) {
       finding(c, "two-length route outside its kernels", p.kernel, p.nv);
     if (p.args.taps != c.Llo || p.args.taps_hi != c.Lhi) finding(c, "two-length route tap counts", p.args.taps, p.args.taps_hi);
     if (p.args.unrolled && !has_unrolled_pair(c.Llo, c.Lhi)) finding(c, "unrolled two-length kernel at an unlisted pair");
-    if (!(tu.bi & 4) && !p.args.unrolled) finding(c, "runtime-L two-length inverse without VW_BI bit 2");
+    if (!(tu.bi & 4) && !p.args.unrolled && !c.off) finding(c, "runtime-L two-length inverse without VW_BI bit 2");
   } else if ((tu.bi & 2) && (tu.bi & 4) && c.Llo != c.Lhi && !pair && p.fused && p.nv != 2 && (p.kernel == kInvSeq || p.kernel == kInvDb)) {
     finding(c, "padded route where the two-length route fits", p.kernel);
   }
@@ -213,9 +218,12 @@ static void walk(const char* dtype) {
               const int J = std::min(5, max_levels(N, std::max(Llo, Lhi)));
               if (J < 1) continue;
               for (unsigned flags : {0u, (unsigned)VW_FLAG_FMA, (unsigned)(VW_FLAG_REF_NONFINITE)}) {
-                Case c{"", dtype, ts.name, N, Llo, Lhi, J, boundary, flags};
-                if (side == 0) forward_case<T>(tu, c);
-                else { inverse_case<T>(tu, c, false); if (flags == 0) inverse_case<T>(tu, c, true); }
+                for (int off : {0, 1, 2, 4, 7}) {  // aligned, every caller pointer alone one element off, all together
+                  if (off && flags == VW_FLAG_REF_NONFINITE) continue;
+                  Case c{"", dtype, ts.name, N, Llo, Lhi, J, boundary, flags, off};
+                  if (side == 0) forward_case<T>(tu, c);
+                  else { inverse_case<T>(tu, c, false); if (flags == 0) inverse_case<T>(tu, c, true); }
+                }
               }
               if (side == 0 && boundary == VW_PERIODIC) {  // the core decompose's flags, up to its level cap
                 const int Jc = max_levels(N, Llo);

@@ -3,7 +3,12 @@
 // the pinned configurations and the padded-layout rule (blk_pad) with its table of values.  Prints nothing when all is well; otherwise one line per finding: the call, the
 // plan as text and the broken rule.  tests/test_plan_cpu.py fails on any output.
 //   plan_check                      the whole matrix and the pins
-//   plan_check show fwd|inv f64|f32 B N L J boundary flags [wid] [VW_KEY=value ...]     one plan as text
+//   plan_check show fwd|inv f64|f32 B N L J boundary flags [wid] [VW_KEY=value ...] [x+8 d+8 a+8 y+8 t+8 ldx=N+3]
+//                                   one plan as text; x / d / a / y / t + bytes: the caller's x, details, approx, y and
+//                                   thresholds that many bytes off a 16-byte boundary (t+ also passes thresholds),
+//                                   ldx=: the forward input's leading dimension, mask=: the inverse's detail mask,
+//                                   az=1: approx_zero with approx = NULL, Lhi=: a two-length bank's high-pass tap
+//                                   count, single=1: the single-level entry points
 #include "../../vectorwave_amd/csrc/vw_plan.h"
 
 #include <cstdio>
@@ -109,6 +114,61 @@ static void finding(const Ctx& c, const std::string& plan, const char* rule) {
 template <typename T> static constexpr int vecw() { return 16 / (int)sizeof(T); }
 static bool plus_zero(const LevelDesc& d) { return d.dir_a == 1 && d.dir_d == 1 && d.off_a == 0 && d.off_d == 0; }
 
+// Rule 8, alignment: what the kernels' loads and stores need, read from their code, not from the planner's conditions.
+//   - store_vec / load_row_regs / tile_to_lds take the 16-byte path when vec_ok, and the tap-unrolled fused kernels
+//     set vec_ok = (L > 0) || vec_io: `unrolled`, `full` and `vec_io` all mean 16-byte accesses at row + w * V.
+//   - k_forward_persist (LDS-DMA of 16 bytes per lane from x + b * ldx), the register-blocked and matrix-core
+//     kernels have no scalar form at all.
+//   - the deep kernels (vw_deep.hip) feed their rings by 16-byte DMA and store whole vectors; k_*_multi and
+//     k_*_level follow their own vec_io, and k_inverse_multi's prefetch / padded layout (pf, pad) loads vectors
+//     unconditionally.
+//   - the column sweeps and the chained sweeps (k_*_sweep, k_inverse_sweep2 / 3) load and store single elements:
+//     they need nothing.
+// A row of a caller array starts at base + b * ld (+ k * B * N for plane k of the details), so base % 16 == 0 with
+// ld % V == 0 and N % V == 0 is what makes every row a whole number of vectors from a 16-byte boundary; the workspace
+// halves (256-byte aligned base, second half one plane on) need N % V == 0 alone.
+static bool al16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
+
+struct Ptrs {  // the caller pointers of one call, as the steps' buffer names see them
+  const void* in;       // forward x, inverse approx (nullptr: none)
+  long long ld_in;      // leading dimension of `in`
+  const void* out;      // forward approx, inverse y
+  const void* details;
+  long long B, N;
+  int elem;
+};
+static bool buf_ok(const Ptrs& q, int b, bool first_level_input) {
+  const int V = 16 / q.elem;
+  if (b == kBufIn) return (!q.in || al16(q.in)) && (!first_level_input || q.ld_in % V == 0);
+  if (b == kBufOut) return al16(q.out);
+  return true;  // workspace halves: N % V == 0, checked by the caller
+}
+static bool plane_ok(const Ptrs& q, int k) { return al16((const char*)q.details + (size_t)k * q.B * q.N * q.elem); }
+
+template <typename T, typename Args>
+static const char* check_step_alignment(const Plan<T, Args>& p, bool inverse, const Ptrs& q) {
+  constexpr int V = vecw<T>();
+  for (const auto& s : p.steps) {
+    bool vec = false;
+    switch (s.kind) {
+      case kStepDeep: vec = true; break;
+      case kStepMulti:
+        if ((s.multi.pf || s.multi.pad) && !s.multi.vec_io) return "8: multi-level prefetch / padded layout without vec_io";
+        vec = s.multi.vec_io != 0;
+        break;
+      case kStepTile: vec = s.lvl.vec_io != 0; break;
+      default: break;  // sweeps: element accesses only
+    }
+    if (!vec) continue;
+    if (q.N % V) return "8: vector I/O on rows that are no whole number of vectors";
+    if (!buf_ok(q, s.src, !inverse)) return "8: vector loads from a misaligned input (or leading dimension)";
+    if (!buf_ok(q, s.dst, false)) return "8: vector stores to a misaligned output";
+    for (int j = s.jlo; j <= s.jhi; ++j)
+      if ((!inverse || p.args.lv[j - 1].use_d) && !plane_ok(q, j - 1)) return "8: vector I/O on a misaligned detail plane";
+  }
+  return nullptr;
+}
+
 // rules 1, 2, 5 and 7 on the per-level path (both directions)
 template <typename T, typename Args>
 static const char* check_steps(const Plan<T, Args>& p, bool inverse, int L, int J, long long B, long long N) {
@@ -186,8 +246,18 @@ static const char* check_forward(const FwdCall<T>& c, const FwdPlan<T>& p) {
                        !(c.hist && c.hist_update && !c.hist_first && !c.hist_snap);
   if (p.ref_nf != may_ref) return "6: fix-up where excluded (or missing)";
   if (const char* r = check_reserve(p, c.B, c.N)) return r;
-  if (!p.fused) return check_steps(p, false, c.L, c.J, c.B, c.N);
+  const Ptrs q{c.x, c.ldx, c.approx, c.details, c.B, c.N, (int)sizeof(T)};
+  if (!p.fused) {
+    if (const char* r = check_steps(p, false, c.L, c.J, c.B, c.N)) return r;
+    return check_step_alignment(p, false, q);
+  }
   const FwdArgs<T>& a = p.args;
+  if (a.vec_io || a.unrolled || p.kernel == kFwdPersist || p.kernel == kFwdBlk || p.kernel == kFwdMfma) {
+    if (c.N % V || c.ldx % V) return "8: vector I/O on rows that are no whole number of vectors";
+    if (!al16(c.x) || !al16(c.approx)) return "8: vector I/O on a misaligned x / approx";
+    for (int j = 0; j < c.J; ++j)
+      if (!plane_ok(q, j)) return "8: vector I/O on a misaligned detail plane";
+  }
   if (p.lds > kLdsBytes || p.lds <= 0) return "2: LDS bytes";
   if (p.threads > kMaxThreads || p.threads < 1) return "2: threads";
   if (c.J > kMaxLevels) return "2: levels on the fused path";
@@ -233,8 +303,18 @@ static const char* check_inverse(const InvCall<T>& c, const InvPlan<T>& p) {
   const bool may_ref = (c.flags & VW_FLAG_REF_NONFINITE) && !c.single_level && c.J >= 2;
   if (p.ref_nf != may_ref) return "6: fix-up where excluded (or missing)";
   if (const char* r = check_reserve(p, c.B, c.N)) return r;
-  if (!p.fused) return check_steps(p, true, c.L, c.J, c.B, c.N);
+  const Ptrs q{c.approx_zero ? nullptr : c.approx, c.N, c.y, c.details, c.B, c.N, (int)sizeof(T)};
+  if (!p.fused) {
+    if (const char* r = check_steps(p, true, c.L, c.J, c.B, c.N)) return r;
+    return check_step_alignment(p, true, q);
+  }
   const InvArgs<T>& a = p.args;
+  if (a.vec_io || a.unrolled || a.full || a.blk || p.kernel == kInvBlk || p.kernel == kInvMfma) {
+    if (c.N % V) return "8: vector I/O on rows that are no whole number of vectors";
+    if (!al16(c.y) || (q.in && !al16(q.in))) return "8: vector I/O on a misaligned approx / y";
+    for (int j = 0; j < c.J; ++j)
+      if (a.lv[j].use_d && !plane_ok(q, j)) return "8: vector I/O on a misaligned detail plane";
+  }
   if (p.lds > kLdsBytes || p.lds <= 0) return "2: LDS bytes";
   if (p.threads > kMaxThreads || p.threads < 1) return "2: threads";
   if (c.J > kMaxLevels) return "2: levels on the fused path";
@@ -279,9 +359,11 @@ static const char* check_inverse(const InvCall<T>& c, const InvPlan<T>& p) {
 template <typename T> static const char* dtype_name() { return sizeof(T) == 8 ? "f64" : "f32"; }
 template <typename T> static T* fake(uintptr_t v) { return reinterpret_cast<T*>(v); }  // never dereferenced
 
+enum { kOffX = 1, kOffDetails = 2, kOffApprox = 4, kOffY = 8, kOffThr = 16 };
+
 struct Axes {  // everything beyond (dtype, L, boundary, N, J, B)
   unsigned flags = 0;
-  int misalign = 0;      // bytes added to one caller pointer (x / approx)
+  int misalign = 0;      // mask of the caller pointers one element off a 16-byte boundary: kOffX ...
   int ld_extra = 0;      // ldx = N + ld_extra
   int hist = 0;          // 0 none, 1 read only (flush), 2 update, 3 update + snapshot, 4 update, first block
   bool thr = false;
@@ -300,7 +382,9 @@ static void run_case(const TuneSet& ts, const Tuning& tu, long long B, long long
   Ctx ctx{"fwd", dtype_name<T>(), ts.name, B, N, N + ax.ld_extra, L, J, boundary, ax.wid, ax.flags, ax.name};
   {
     FwdCall<T> c;
-    c.x = fake<T>(0x100000 + ax.misalign); c.details = fake<T>(0x200000); c.approx = fake<T>(0x300000);
+    auto off = [&](int bit) { return (ax.misalign & bit) ? sizeof(T) : 0; };
+    c.x = fake<T>(0x100000 + off(kOffX)); c.details = fake<T>(0x200000 + off(kOffDetails));
+    c.approx = fake<T>(0x300000 + off(kOffApprox));
     c.B = B; c.N = N; c.ldx = N + ax.ld_extra; c.L = L; c.boundary = boundary; c.J = J;
     c.flags = ax.single ? ax.flags & ~VW_FLAG_FFT_SWITCH : ax.flags;
     c.single_level = ax.single;
@@ -314,11 +398,13 @@ static void run_case(const TuneSet& ts, const Tuning& tu, long long B, long long
   }
   {
     InvCall<T> c;
-    c.details = fake<T>(0x200000); c.approx = fake<T>(0x300000 + ax.misalign); c.y = fake<T>(0x400000);
+    auto off = [&](int bit) { return (ax.misalign & bit) ? sizeof(T) : 0; };
+    c.details = fake<T>(0x200000 + off(kOffDetails)); c.approx = fake<T>(0x300000 + off(kOffApprox));
+    c.y = fake<T>(0x400000 + off(kOffY));
     c.B = B; c.N = N; c.L = L; c.wid = ax.wid; c.boundary = boundary; c.J = J;
     c.flags = ax.flags & ~(VW_FLAG_VALIDATE | VW_FLAG_FFT_SWITCH);
     c.detail_mask = ax.single ? 1u : ax.mask; c.single_level = ax.single;
-    if (ax.thr) { c.thr = fake<T>(0x500000); c.soft = 1; c.thr_ld = B; }
+    if (ax.thr) { c.thr = fake<T>(0x500000 + off(kOffThr)); c.soft = 1; c.thr_ld = B; }
     InvPlan<T> p;
     plan_inverse(tu, c, &p);
     ctx.dir = "inv";
@@ -351,8 +437,15 @@ static void run_matrix() {
     a.flags = VW_FLAG_REF_NONFINITE | VW_FLAG_VALIDATE; a.name = "ref_nf+validate"; rest.push_back(a);
     a.flags = VW_FLAG_FFT_SWITCH; a.name = "fft"; rest.push_back(a);
     a.flags = VW_FLAG_FFT_SWITCH | VW_FLAG_REF_NONFINITE; a.name = "fft+ref_nf"; rest.push_back(a);
-    a = Axes(); a.misalign = 8; a.name = "ptr+8"; rest.push_back(a);
-    a.flags = VW_FLAG_REF_NONFINITE; a.name = "ptr+8 ref_nf"; rest.push_back(a);
+    // every caller pointer alone, and all together, one element off a 16-byte boundary
+    static const struct { int mask; const char* name; } kOffsets[] = {
+        {kOffX, "x+1"}, {kOffDetails, "details+1"}, {kOffApprox, "approx+1"}, {kOffY, "y+1"}, {kOffThr, "thr+1"},
+        {kOffX | kOffDetails | kOffApprox | kOffY | kOffThr, "all+1"}};
+    for (const auto& o : kOffsets) {
+      a = Axes(); a.misalign = o.mask; a.thr = (o.mask & kOffThr) != 0; a.name = o.name; rest.push_back(a);
+    }
+    a = Axes(); a.misalign = kOffX | kOffApprox; a.flags = VW_FLAG_REF_NONFINITE; a.name = "x+1 approx+1 ref_nf"; rest.push_back(a);
+    a = Axes(); a.misalign = kOffDetails; a.mask = 0x15u; a.name = "details+1 mask"; rest.push_back(a);
     a = Axes(); a.ld_extra = 1; a.name = "ldx=N+1"; rest.push_back(a);
     for (int h = 1; h <= 4; ++h)
       for (unsigned f : {0u, (unsigned)VW_FLAG_REF_NONFINITE}) {
@@ -479,15 +572,53 @@ static void run_pad_pins() {
   }
 }
 
+// What `show` adds to describe(): the flags that choose between a kernel's vector and element forms.
+template <typename T, typename Args>
+static std::string io_flags(const Plan<T, Args>& p, int full) {
+  char b[96];
+  if (p.error != VW_OK) return "";
+  if (p.fused) {
+    snprintf(b, sizeof(b), " vec_io=%d unrolled=%d full=%d", p.args.vec_io, p.args.unrolled, full);
+    return b;
+  }
+  std::string s = " vec_io=[";
+  for (const auto& st : p.steps) {
+    if (s.back() != '[') s += ' ';
+    s += st.kind == kStepDeep ? "1" : st.kind == kStepMulti ? (st.multi.vec_io ? "1" : "0")
+         : st.kind == kStepTile ? (st.lvl.vec_io ? "1" : "0") : "-";
+  }
+  return s + "]";
+}
+
 template <typename T>
 static int show(bool inverse, char** v, int n) {
   if (n < 6) return 2;
   Tuning tu;
-  int wid = VW_WID_OTHER;
+  int wid = VW_WID_OTHER, az = 0, Lhi = 0, single = 0;
+  long long ox = 0, od = 0, oa = 0, oy = 0, ot = -1, ldx = 0;
+  unsigned mask = ~0u;
   for (int i = 6; i < n; ++i) {
+    char* plus = strchr(v[i], '+');
+    if (plus && plus == v[i] + 1) {  // x+8: a pointer's byte offset
+      const long long o = atoll(plus + 1);
+      switch (v[i][0]) {
+        case 'x': ox = o; break;
+        case 'd': od = o; break;
+        case 'a': oa = o; break;
+        case 'y': oy = o; break;
+        case 't': ot = o; break;
+        default: printf("unknown pointer %s\n", v[i]); return 2;
+      }
+      continue;
+    }
     char* eq = strchr(v[i], '=');
     if (!eq) { wid = atoi(v[i]); continue; }
     *eq = '\0';
+    if (!strcmp(v[i], "ldx")) { ldx = atoll(eq + 1); continue; }
+    if (!strcmp(v[i], "mask")) { mask = (unsigned)strtoul(eq + 1, nullptr, 0); continue; }
+    if (!strcmp(v[i], "az")) { az = atoi(eq + 1); continue; }
+    if (!strcmp(v[i], "Lhi")) { Lhi = atoi(eq + 1); continue; }        // a two-length bank's high-pass taps
+    if (!strcmp(v[i], "single")) { single = atoi(eq + 1); continue; }  // vw_modwt1_*: the single-level calls
     if (!set_tuning(tu, v[i], atoi(eq + 1))) { printf("unknown switch %s\n", v[i]); return 2; }
   }
   const long long B = atoll(v[0]), N = atoll(v[1]);
@@ -495,18 +626,23 @@ static int show(bool inverse, char** v, int n) {
   const unsigned flags = (unsigned)strtoul(v[5], nullptr, 0);
   if (inverse) {
     InvCall<T> c;
-    c.details = fake<T>(0x200000); c.approx = fake<T>(0x300000); c.y = fake<T>(0x400000);
+    c.details = fake<T>(0x200000 + od); c.approx = az ? nullptr : fake<T>(0x300000 + oa); c.y = fake<T>(0x400000 + oy);
     c.B = B; c.N = N; c.L = L; c.wid = wid; c.boundary = boundary; c.J = J; c.flags = flags;
+    c.detail_mask = mask; c.approx_zero = az; c.Lhi = Lhi; c.single_level = single != 0;
+    if (ot >= 0) { c.thr = fake<T>(0x500000 + ot); c.soft = 1; c.thr_ld = B; }
     InvPlan<T> p;
     plan_inverse(tu, c, &p);
-    printf("%s\n", describe(p, true).c_str());
+    printf("%s%s\n", describe(p, true).c_str(), io_flags(p, p.args.full).c_str());
+    if (const char* r = check_inverse(c, p)) { printf("%s\n", r); return 1; }
   } else {
     FwdCall<T> c;
-    c.x = fake<T>(0x100000); c.details = fake<T>(0x200000); c.approx = fake<T>(0x300000);
-    c.B = B; c.N = N; c.ldx = N; c.L = L; c.boundary = boundary; c.J = J; c.flags = flags;
+    c.x = fake<T>(0x100000 + ox); c.details = fake<T>(0x200000 + od); c.approx = fake<T>(0x300000 + oa);
+    c.B = B; c.N = N; c.ldx = ldx ? ldx : N; c.L = L; c.boundary = boundary; c.J = J; c.flags = flags;
+    c.Lhi = Lhi; c.single_level = single != 0;
     FwdPlan<T> p;
     plan_forward(tu, c, &p);
-    printf("%s\n", describe(p, false).c_str());
+    printf("%s%s\n", describe(p, false).c_str(), io_flags(p, 0).c_str());
+    if (const char* r = check_forward(c, p)) { printf("%s\n", r); return 1; }
   }
   return 0;
 }

@@ -21,13 +21,13 @@ struct Case {
   const char* dtype;
   const char* tune;
   long long N, B;
-  int L, J, boundary, aligned;
+  int L, J, boundary, off;  // off: mask of the caller pointers one element off a 16-byte boundary (1 details, 2 approx, 4 y)
   unsigned flags;
 };
 static void finding(const Case& c, const char* rule, long long a = 0, long long b = 0) {
   if (++g_findings > 100) return;
-  printf("%s N=%lld B=%lld L=%d J=%d boundary=%d flags=0x%x aligned=%d [%s] | %s (%lld, %lld)\n", c.dtype, c.N, c.B, c.L,
-         c.J, c.boundary, c.flags, c.aligned, c.tune, rule, a, b);
+  printf("%s N=%lld B=%lld L=%d J=%d boundary=%d flags=0x%x off=%d [%s] | %s (%lld, %lld)\n", c.dtype, c.N, c.B, c.L,
+         c.J, c.boundary, c.flags, c.off, c.tune, rule, a, b);
 }
 
 template <typename T>
@@ -35,7 +35,8 @@ static void one_case(const Tuning& tu, const Case& c, bool single = false) {
   constexpr int V = 16 / (int)sizeof(T);
   alignas(16) static T dummy[8];
   InvCall<T> k;
-  k.details = dummy; k.approx = dummy; k.y = c.aligned ? dummy : dummy + 1;  // never dereferenced by the planner
+  k.details = dummy + (c.off & 1); k.approx = dummy + ((c.off >> 1) & 1); k.y = dummy + ((c.off >> 2) & 1);  // never dereferenced by the planner
+  const bool aligned = c.off == 0;
   k.B = c.B; k.N = c.N; k.L = c.L; k.boundary = c.boundary; k.J = c.J; k.flags = c.flags; k.cus = 256;
   k.single_level = single;
   MraPlan<T> p;
@@ -47,7 +48,7 @@ static void one_case(const Tuning& tu, const Case& c, bool single = false) {
   // rows, a listed length) and k_mra has none for the length (past kMraUnrollMax); VW_MRA_FUSED=2 fuses there too
   const long long th4 = (nvec + 3) / 4, nv_want = th4 > 512 ? 8 : tu.nv;
   const long long th_want = ((nvec + nv_want - 1) / nv_want + 63) / 64 * 64;
-  const bool slow = tu.mra_fused == 1 && c.aligned && c.N % V == 0 && (nv_want - 1) * th_want <= nvec &&
+  const bool slow = tu.mra_fused == 1 && aligned && c.N % V == 0 && (nv_want - 1) * th_want <= nvec &&
                     has_unrolled_taps(c.L) && c.L <= tu.unroll_max && c.L > kMraUnrollMax;
   if (!p.fused) {
     ++g_loop;
@@ -75,7 +76,7 @@ static void one_case(const Tuning& tu, const Case& c, bool single = false) {
   if (a.N != c.N || a.B != c.B || a.J != c.J || a.taps != c.L) finding(c, "shape not carried");
   if (a.hlpad % V || a.region1 % V) finding(c, "region offsets not whole vectors", a.hlpad, a.region1);
   if ((long long)p.lds != 2LL * a.region1 * (long long)sizeof(T)) finding(c, "LDS is not two regions", p.lds, a.region1);
-  const bool io = c.aligned && c.N % V == 0;
+  const bool io = aligned && c.N % V == 0;  // k_mra reads the details and the approximation and writes y as vectors
   if ((a.vec_io != 0) != io) finding(c, "vec_io does not follow the alignment", a.vec_io);
   if (a.unrolled) {
     if (!io) finding(c, "unrolled on unaligned rows");
@@ -126,10 +127,10 @@ static void walk(const char* dtype) {
           const int cap = max_levels(N, L);
           for (int J = 1; J <= std::min(cap + 2, kMaxLevels); ++J)
             for (unsigned flags : {0u, (unsigned)VW_FLAG_FMA, (unsigned)VW_FLAG_VALIDATE, (unsigned)VW_FLAG_REF_NONFINITE})
-              for (int aligned = 0; aligned < 2; ++aligned) {
-                const Case c{dtype, ts.name, N, (N & 1) ? 3 : 1031, L, J, boundary, aligned, flags};
+              for (int off : {0, 1, 2, 4, 7}) {  // aligned, every pointer alone, all together
+                const Case c{dtype, ts.name, N, (N & 1) ? 3 : 1031, L, J, boundary, off, flags};
                 one_case<T>(tu, c);
-                if (J == 1 && flags == 0 && aligned) one_case<T>(tu, c, true);
+                if (J == 1 && flags == 0 && off == 0) one_case<T>(tu, c, true);
               }
         }
   }

@@ -222,6 +222,14 @@ __global__ void __launch_bounds__(256) k_energy_rows_tree(const EnergyPlanesArgs
         s += v[0] * v[0];
         s += v[1] * v[1];
       }
+    } else if (N % 2 == 0) {
+      // rows that are not 16-byte aligned: the vector form's partial sums, element by element -- which terms a
+      // thread adds, and in what order, must not depend on where the caller's arrays start
+#pragma unroll 4
+      for (int i = tid; i < N / 2; i += 256) {
+        s += row[2 * i] * row[2 * i];
+        s += row[2 * i + 1] * row[2 * i + 1];
+      }
     } else {
 #pragma unroll 4
       for (int i = tid; i < N; i += 256) s += row[i] * row[i];
