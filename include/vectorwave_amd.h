@@ -383,6 +383,51 @@ VW_API vw_status vw_cwt_f32(vw_ctx *ctx, const float *x, int64_t B, int64_t N, i
                             const vw_cwt_scale *scales, int S, const double *taps_re, const double *taps_im,
                             int64_t ntaps, int ext, int64_t wrap, unsigned flags, float *out_re, float *out_im);
 
+/* ---- inverse continuous wavelet transform ----------------------------------------------------------
+ * InverseCWT.reconstruct / reconstructBand (cwt/InverseCWT.java) for a batch of coefficient planes coef [B][S][ldc]
+ * (what vw_cwt_* writes when ldc == N) into rows out [B][ldo], table-driven like vw_cwt_*.  scales[j] =
+ * {tap_begin, taps K_j, window_begin o_j, plane, weight, scale}: descriptor j reads plane `plane` of every row, so a
+ * band is a descriptor list over a subset of the planes, with no copy.  w_j[k] = taps[tap_begin + k], a table of
+ * ntaps doubles on the HOST whatever the flags (rounded to float once by the _f32 call; weight, scale and divisor too).
+ *
+ *   VW_ICWT_SUM     out[b][tau] = ( sum_j weight_j * ( sum_{k=0}^{K_j-1} w_j[k] * z_{b,plane_j}[(tau + o_j + k) mod wrap] ) ) / divisor
+ *                   z = the plane's row, zero on [N, wrap).  j ascends in descriptor order, k ascends; each descriptor has
+ *                   its own accumulator started at +0.0, and one outer accumulator started at +0.0 takes
+ *                   total = total + acc_j * weight_j.  Without VW_FLAG_FMA multiply and add are separate roundings,
+ *                   inner and outer; with it each is one fma.  One IEEE division per output.  `scale` is not read.
+ *                   This is the sum reconstructInternalRealFFT (:225-270, N >= 128) evaluates by FFT: with
+ *                   g_j(d) = psi(d / a_j) / sqrt(a_j), d in (-M/2, M/2], cut to [d_min, d_max] at its outermost non-zero
+ *                   entries: o_j = -d_max, w_j[k] = g_j(d_max - k), weight_j = weights[j] / a_j (divided in double,
+ *                   :238), wrap = M = nextPowerOfTwo(N), divisor = C_psi.  The reference's FFT differs from the sum
+ *                   by its own rounding.
+ *   VW_ICWT_DIRECT  reconstructInternalRealDirect (:283-311, N < 128) literally, in the element type: per output t one
+ *                   accumulator over the descriptors and b = 0..N-1 ascending,
+ *                   sum += ((c * w_j[t - b + N - 1]) * weight_j) / scale_j with c = coef[b'][plane_j][b], terms with
+ *                   fabs(c) < 1e-10 skipped (a NaN is not), then / divisor.  K_j = 2N - 1; o_j and wrap are not read.
+ * Flags: VW_FLAG_FMA (SUM only), VW_FLAG_HOST_MEMORY, VW_FLAG_SYNC; any other is VW_ERR_ARG.
+ * Errors, all before any device work: null pointers VW_ERR_NULL; B, S, N or nsc = 0 VW_ERR_EMPTY; ldc < N, ldo < N,
+ * K_j < 1, a descriptor reaching outside [0, ntaps), plane outside [0, S), |o_j| > 2^30, divisor <= 0 (or NaN),
+ * wrap < N in SUM, K_j != 2N - 1 or VW_FLAG_FMA in DIRECT, an unknown form -> VW_ERR_ARG; K_j > 16384 ->
+ * VW_ERR_UNSUPPORTED naming the descriptor.
+ * The table and descriptors are kept on the device between calls in a slot of their own (vw_cwt_* and vw_icwt_*
+ * calls do not evict each other's): a call with the same ones uploads nothing, and only such a call can be
+ * recorded into a vw_graph (VW_ERR_STATE otherwise).  Timing family: "icwt". */
+enum { VW_ICWT_SUM = 0, VW_ICWT_DIRECT = 1 };
+typedef struct vw_icwt_scale {
+    int64_t tap_begin;
+    int32_t taps;
+    int32_t window_begin;
+    int32_t plane;
+    double weight;
+    double scale;
+} vw_icwt_scale;
+VW_API vw_status vw_icwt_f64(vw_ctx *ctx, const double *coef, int64_t B, int S, int64_t N, int64_t ldc,
+                             const vw_icwt_scale *scales, int nsc, const double *taps, int64_t ntaps, int form,
+                             int64_t wrap, double divisor, unsigned flags, double *out, int64_t ldo);
+VW_API vw_status vw_icwt_f32(vw_ctx *ctx, const float *coef, int64_t B, int S, int64_t N, int64_t ldc,
+                             const vw_icwt_scale *scales, int nsc, const double *taps, int64_t ntaps, int form,
+                             int64_t wrap, double divisor, unsigned flags, float *out, int64_t ldo);
+
 /* ---- one batch over several contexts (one host thread per context) ----------------------------
  * Replaces the reference's in-process parallelism over one batch call: BatchMODWT.multiLevelAoS /
  * inverseMultiLevelAoS (ext/extensions/modwt/BatchMODWT.java:90-111, :151-178) and the

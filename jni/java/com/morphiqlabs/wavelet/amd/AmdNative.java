@@ -147,6 +147,13 @@ public final class AmdNative {
     static native int cwtAoS(long ctx, double[][] rows, long[] scaleDesc, double[] divisors, double[] tapsRe,
                              double[] tapsIm, int ext, long wrap, int flags, double[] outRe, double[] outIm);
 
+    // inverse continuous wavelet transform (out: B * N doubles, [B][N]): planeRows holds B * S rows, row b * S + s the
+    // plane s of signal b; scaleDesc {tap_begin, taps, window_begin, plane} and weights {weight, scale} per descriptor,
+    // taps the flat table; form ICWT_SUM (wrap: the period M) or ICWT_DIRECT; divisor the admissibility constant
+    public static final int ICWT_SUM = 0, ICWT_DIRECT = 1;
+    static native int icwtAoS(long ctx, double[][] planeRows, int numPlanes, long[] scaleDesc, double[] weights,
+                              double[] taps, int form, long wrap, double divisor, int flags, double[] out);
+
     // com.morphiqlabs.financial: FinancialAnalyzer's four metrics + the detail standard deviation of every price
     // row (out: 5 * B doubles, [5][B]); FinancialWaveletAnalyzer's Sharpe ratios of every return row (out: B)
     static native int finAnalyzeAoS(long ctx, double[][] prices, double[] lo, double[] hi, double anomalyK, int flags,

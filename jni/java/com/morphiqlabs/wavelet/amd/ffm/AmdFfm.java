@@ -44,6 +44,8 @@ public final class AmdFfm implements AutoCloseable {
     private final MethodHandle forwardBi, inverseBi;
     /** vw_cwt_f64: the continuous wavelet transform over host segments ({@link #cwtHost}). */
     private final MethodHandle cwt;
+    /** vw_icwt_f64: the inverse continuous wavelet transform over host segments ({@link #icwtHost}). */
+    private final MethodHandle icwt;
     private final MemorySegment ctx;
 
     /** Loads {@code libvectorwave_amd.so} from {@code libraryPath} and creates a context on {@code device}. */
@@ -74,6 +76,10 @@ public final class AmdFfm implements AutoCloseable {
         // vw_cwt_f64(ctx, x, B, N, ldx, scales, S, taps_re, taps_im, ntaps, ext, wrap, flags, out_re, out_im)
         cwt = fn("vw_cwt_f64", FunctionDescriptor.of(JAVA_INT, ADDRESS, ADDRESS, JAVA_LONG, JAVA_LONG, JAVA_LONG, ADDRESS,
                 JAVA_INT, ADDRESS, ADDRESS, JAVA_LONG, JAVA_INT, JAVA_LONG, JAVA_INT, ADDRESS, ADDRESS));
+        // vw_icwt_f64(ctx, coef, B, S, N, ldc, scales, nsc, taps, ntaps, form, wrap, divisor, flags, out, ldo)
+        icwt = fn("vw_icwt_f64", FunctionDescriptor.of(JAVA_INT, ADDRESS, ADDRESS, JAVA_LONG, JAVA_INT, JAVA_LONG, JAVA_LONG,
+                ADDRESS, JAVA_INT, ADDRESS, JAVA_LONG, JAVA_INT, JAVA_LONG, ValueLayout.JAVA_DOUBLE, JAVA_INT, ADDRESS,
+                JAVA_LONG));
         // vw_swt_denoise_f64(ctx, x, B, N, ldx, lo, hi, L, wavelet_id, boundary, J, threshold, soft, flags, y, thr)
         denoise = fn("vw_swt_denoise_f64", FunctionDescriptor.of(JAVA_INT, ADDRESS, ADDRESS, JAVA_LONG, JAVA_LONG,
                 JAVA_LONG, ADDRESS, ADDRESS, JAVA_INT, JAVA_INT, JAVA_INT, JAVA_INT, ValueLayout.JAVA_DOUBLE, JAVA_INT,
@@ -159,6 +165,37 @@ public final class AmdFfm implements AutoCloseable {
             check((int) cwt.invokeExact(ctx, x, B, N, N, sc, S, taps(a, tapsRe),
                     tapsIm == null ? MemorySegment.NULL : taps(a, tapsIm), (long) tapsRe.length, ext, wrap,
                     flags | FLAG_HOST_MEMORY | FLAG_SYNC, outRe, tapsIm == null ? MemorySegment.NULL : outIm));
+        } catch (Throwable t) {
+            throw rethrow(t);
+        }
+    }
+
+    /**
+     * InverseCWT.reconstruct over host segments: coef [B][S][N] -> out [B][N].  Descriptor j reads {@code taps[j]}
+     * values from {@code tapBegin[j]} of the flat table and plane {@code plane[j]} of every signal; in the SUM form
+     * (form 0) its window starts at {@code tau + windowBegin[j]} over the period {@code wrap} and its sum is weighted by
+     * {@code weights[j]}; the DIRECT form (form 1) divides every term by {@code scales[j]} (vw_icwt_scale;
+     * AmdInverseCWT builds them).  {@code divisor}: the admissibility constant.
+     */
+    public void icwtHost(MemorySegment coef, long B, int S, long N, long[] tapBegin, int[] taps, int[] windowBegin,
+                         int[] plane, double[] weights, double[] scales, double[] table, int form, long wrap,
+                         double divisor, int flags, MemorySegment out) {
+        final int D = weights.length;
+        requireBytes(coef, B * S * N, "coef");
+        requireBytes(out, B * N, "out");
+        try (Arena a = Arena.ofConfined()) {
+            MemorySegment sc = a.allocate(40L * D, 8);   // vw_icwt_scale: int64, int32, int32, int32, (pad), double, double
+            for (int j = 0; j < D; j++) {
+                sc.set(JAVA_LONG, 40L * j, tapBegin[j]);
+                sc.set(JAVA_INT, 40L * j + 8, taps[j]);
+                sc.set(JAVA_INT, 40L * j + 12, windowBegin[j]);
+                sc.set(JAVA_INT, 40L * j + 16, plane[j]);
+                sc.set(JAVA_INT, 40L * j + 20, 0);
+                sc.set(ValueLayout.JAVA_DOUBLE, 40L * j + 24, weights[j]);
+                sc.set(ValueLayout.JAVA_DOUBLE, 40L * j + 32, scales[j]);
+            }
+            check((int) icwt.invokeExact(ctx, coef, B, S, N, N, sc, D, taps(a, table), (long) table.length, form, wrap,
+                    divisor, flags | FLAG_HOST_MEMORY | FLAG_SYNC, out, N));
         } catch (Throwable t) {
             throw rethrow(t);
         }

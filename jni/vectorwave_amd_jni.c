@@ -869,6 +869,62 @@ JNIEXPORT jint JNICALL VW_JNI(cwtAoS)(JNIEnv *e, jclass c, jlong ctx, jobjectArr
   return st;
 }
 
+/* ---- inverse continuous wavelet transform: out = B * N doubles, [B][N] ----
+ * planeRows double[B * S][N]: row b * S + s is plane s of signal b (the rows of B CWT results, by reference);
+ * scaleDesc long[4 D] = {tap_begin, taps, window_begin, plane} per descriptor and weights double[2 D] = {weight, scale}
+ * (the fields of vw_icwt_scale); taps the flat table.  Row chunks as cwtAoS, over signals: a chunk gathers the S planes
+ * of nb signals.  The table is copied once per call; the context keeps it on the device from chunk to chunk. */
+JNIEXPORT jint JNICALL VW_JNI(icwtAoS)(JNIEnv *e, jclass c, jlong ctx, jobjectArray planeRows, jint S,
+                                       jlongArray scaleDesc, jdoubleArray weights, jdoubleArray taps, jint form,
+                                       jlong wrap, jdouble divisor, jint flags, jdoubleArray out) {
+  (void)c;
+  if (!scaleDesc || !weights) return null_error(e, "Scales cannot be null");
+  if (!taps) return null_error(e, "wavelet tables cannot be null");
+  const jsize D = (*e)->GetArrayLength(e, weights) / 2;
+  if (D < 1 || S < 1) return arg_error(e, "Scales cannot be empty");
+  if ((*e)->GetArrayLength(e, weights) != 2 * D || (*e)->GetArrayLength(e, scaleDesc) != 4 * D)
+    return arg_error(e, "scaleDesc must hold 4 values and weights 2 values per scale");
+  const jsize ntaps = (*e)->GetArrayLength(e, taps);
+  if (ntaps < 1) return arg_error(e, "wavelet tables must be non-empty");
+  const jsize N = row_len(e, planeRows);
+  if (N < 1) return VW_ERR_ARG;
+  const jsize R = (*e)->GetArrayLength(e, planeRows);
+  if (R % S != 0) return arg_error(e, "coefficient rows must be S per signal");
+  const jsize B = R / S;
+  if (!fin_out_ok(e, out, (size_t)B * (size_t)N)) return VW_ERR_ARG;
+  const jsize CB = chunk_rows(((size_t)S + 1) * (size_t)N, B);
+  int oom = 0;
+  double *pc = out_buf(0, (size_t)CB * S * N, &oom), *po = out_buf(1, (size_t)CB * N, &oom);
+  vw_icwt_scale *sc = (vw_icwt_scale *)malloc((size_t)D * sizeof(vw_icwt_scale));
+  jlong *ld = (jlong *)malloc((size_t)4 * D * sizeof(jlong));
+  double *tab = (double *)malloc(((size_t)ntaps + 2 * (size_t)D) * sizeof(double));
+  if (oom || !sc || !ld || !tab) { free(sc); free(ld); free(tab); return oom_error(e); }
+  double *w = tab + ntaps;
+  (*e)->GetLongArrayRegion(e, scaleDesc, 0, 4 * D, ld);
+  (*e)->GetDoubleArrayRegion(e, weights, 0, 2 * D, w);
+  (*e)->GetDoubleArrayRegion(e, taps, 0, ntaps, tab);
+  vw_status st = VW_OK;
+  for (jsize j = 0; j < D; ++j) {
+    const jlong k = ld[4 * j + 1], o = ld[4 * j + 2], p = ld[4 * j + 3];
+    if (k < 1 || k > 0x7fffffff || o > 0x7fffffff || o < -0x7fffffff || p < 0 || p > 0x7fffffff) {
+      st = arg_error(e, "scale descriptor out of range");
+      break;
+    }
+    sc[j].tap_begin = ld[4 * j]; sc[j].taps = (int32_t)k; sc[j].window_begin = (int32_t)o; sc[j].plane = (int32_t)p;
+    sc[j].weight = w[2 * j]; sc[j].scale = w[2 * j + 1];
+  }
+  for (jsize b0 = 0; b0 < B && st == VW_OK; b0 += CB) {
+    const jsize nb = B - b0 < CB ? B - b0 : CB;
+    if (!gather_rows(e, planeRows, b0 * S, nb * S, N, pc)) { st = VW_ERR_ARG; break; }
+    st = vw_icwt_f64(CTX(ctx), pc, nb, S, N, N, sc, D, tab, ntaps, form, wrap, divisor, (unsigned)flags | HOST_FLAGS, po, N);
+    if (st != VW_OK) break;
+    (*e)->SetDoubleArrayRegion(e, out, (jsize)((size_t)b0 * N), (jsize)((size_t)nb * N), po);
+  }
+  free(sc); free(ld); free(tab);
+  trim_slots();
+  return st;
+}
+
 /* lo == NULL: vw_fin_sharpe_f64; else vw_fin_wavelet_sharpe_f64 */
 static jint fin_sharpe_rows(JNIEnv *e, jlong ctx, jobjectArray returns, const Taps *tl, const Taps *th, jint boundary,
                             jdouble riskFree, jint flags, jdoubleArray out) {

@@ -13,12 +13,12 @@ include/vectorwave_amd.h).  This package is the host-side mirror of the referenc
   Haar, Daubechies, Symlet, Coiflet, BiorthogonalSpline,
   ReverseBiorthogonalSpline                                   (core/api wavelets)
   CWTTransform, CWTConfig, CWTResult, ScaleSpace, MorletWavelet,
-  RickerWavelet, PaulWavelet, DOGWavelet                      (core/cwt, core/cwt/finance)
+  RickerWavelet, PaulWavelet, DOGWavelet, InverseCWT          (core/cwt, core/cwt/finance)
 """
 from .wavelets import (BiorthogonalSpline, BiorthogonalWavelet, Coiflet, Daubechies, Haar, ReverseBiorthogonalSpline,
                        Symlet, Wavelet, available_wavelets, get_wavelet)
-from .errors import (ErrorCode, InvalidArgumentException, InvalidSignalException, InvalidStateException,
-                     WaveletTransformException)
+from .errors import (ErrorCode, InvalidArgumentException, InvalidConfigurationException, InvalidSignalException,
+                     InvalidStateException, WaveletTransformException)
 from .modwt import (BoundaryMode, MODWTResult, MODWTTransform, MultiLevelMODWTResult, MultiLevelMODWTTransform,
                     MutableMultiLevelMODWTResult)
 from .swt import VectorWaveSwtAdapter
@@ -31,7 +31,7 @@ from .financial import (FinancialAnalysisConfig, FinancialAnalyzer, FinancialCon
 from .engine import Engine, max_levels, version
 from .multidevice import DeviceGroup
 from .cwt import (ComplexContinuousWavelet, ContinuousWavelet, CWTConfig, CWTResult, CWTTransform, DOGWavelet,
-                  MorletWavelet, PaddingStrategy, PaulWavelet, RickerWavelet, ScaleSpace)
+                  InverseCWT, MorletWavelet, PaddingStrategy, PaulWavelet, RickerWavelet, ScaleSpace)
 
 __all__ = [
     "Coiflet", "Daubechies", "Haar", "Symlet", "Wavelet", "available_wavelets", "get_wavelet",
@@ -44,5 +44,6 @@ __all__ = [
     "FinancialAnalysisConfig", "FinancialAnalyzer", "FinancialConfig", "FinancialWaveletAnalyzer",
     "VolatilityClassification", "BiorthogonalSpline", "BiorthogonalWavelet", "ReverseBiorthogonalSpline",
     "ComplexContinuousWavelet", "ContinuousWavelet", "CWTConfig", "CWTResult", "CWTTransform", "DOGWavelet",
-    "MorletWavelet", "PaddingStrategy", "PaulWavelet", "RickerWavelet", "ScaleSpace",
+    "MorletWavelet", "PaddingStrategy", "PaulWavelet", "RickerWavelet", "ScaleSpace", "InverseCWT",
+    "InvalidConfigurationException",
 ]

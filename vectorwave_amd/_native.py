@@ -35,6 +35,15 @@ class CwtScale(ctypes.Structure):
     _fields_ = [("tap_begin", c_int64), ("taps", ctypes.c_int32), ("window_begin", ctypes.c_int32),
                 ("divisor", c_double)]
 
+
+# inverse continuous wavelet transform: forms and the per-scale descriptor (vw_icwt_scale)
+ICWT_SUM, ICWT_DIRECT = 0, 1
+
+
+class IcwtScale(ctypes.Structure):
+    _fields_ = [("tap_begin", c_int64), ("taps", ctypes.c_int32), ("window_begin", ctypes.c_int32),
+                ("plane", ctypes.c_int32), ("weight", c_double), ("scale", c_double)]
+
 # Every symbol include/vectorwave_amd.h declares, with its ctypes signature.
 _dp = POINTER(c_double)
 _fp = POINTER(c_float)
@@ -105,6 +114,11 @@ SIGNATURES = {
                            c_int, c_int64, c_uint, c_void_p, c_void_p]),
     "vw_cwt_f32": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int64, POINTER(CwtScale), c_int, _dp, _dp, c_int64,
                            c_int, c_int64, c_uint, c_void_p, c_void_p]),
+    # inverse: coef [B][S][ldc], (scales, nsc, taps, ntaps, form, wrap, divisor), out [B][ldo]
+    "vw_icwt_f64": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_int64, c_int64, POINTER(IcwtScale), c_int, _dp, c_int64,
+                            c_int, c_int64, c_double, c_uint, c_void_p, c_int64]),
+    "vw_icwt_f32": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_int64, c_int64, POINTER(IcwtScale), c_int, _dp, c_int64,
+                            c_int, c_int64, c_double, c_uint, c_void_p, c_int64]),
     "vw_fin_analyze_f64": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int64, _dp, _dp, c_int, c_double, c_uint,
                                    c_void_p]),
     "vw_fin_sharpe_f64": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int64, c_double, c_uint, c_void_p]),

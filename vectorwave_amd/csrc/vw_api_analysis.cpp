@@ -1,5 +1,5 @@
 // vw_api_analysis.cpp -- the analysis entry points of the C ABI: financial metrics, wavelet energy per level,
-// multiresolution analysis and the continuous wavelet transform.
+// multiresolution analysis, the continuous wavelet transform and its inverse.
 #include "vw_host.h"
 
 using namespace vw;
@@ -361,6 +361,29 @@ extern "C" vw_status vw_modwt_mra_f32(vw_ctx* c, const float* x, int64_t B, int6
 // Continuous wavelet transform (vw_cwt.hip): fixed-order correlations of each row with one table per scale, plan_cwt's
 // launches heaviest scales first.  Timing family: "cwt".
 
+// A call's table image `img` (its first `bytes` go to the device) into a slot of the context: *dev of *dev_bytes,
+// *resident the host image it holds.  The same image again uploads nothing.  A new one bumps ws_gen (graphs
+// recorded on the old tables are stale) and cannot be recorded.
+static vw_status image_upload(vw_ctx* c, void** dev, size_t* dev_bytes, std::vector<unsigned char>* resident,
+                              std::vector<unsigned char>* img, size_t bytes, const char* who) {
+  if (*img == *resident) return VW_OK;
+  if (c->capturing)
+    return fail(VW_ERR_STATE, "%s: new tables cannot be uploaded during a capture (run the call once first)", who);
+  if (*dev_bytes < bytes) {
+    VW_HIP(hipStreamSynchronize(c->stream));
+    if (*dev) hipFree(*dev);
+    *dev = nullptr; *dev_bytes = 0; resident->clear();
+    VW_HIP(hipMalloc(dev, bytes));
+    *dev_bytes = bytes;
+  }
+  resident->clear();  // (not valid until the copy is enqueued)
+  VW_HIP(hipMemcpyAsync(*dev, img->data(), bytes, hipMemcpyHostToDevice, c->stream));
+  VW_HIP(hipStreamSynchronize(c->stream));  // img is this call's
+  resident->swap(*img);
+  ++c->ws_gen;
+  return VW_OK;
+}
+
 // The call's device image: [CwtScaleDev x S, plan order][taps_re x ntaps][taps_im x ntaps], T-typed, 16-byte aligned
 // parts.  Kept in the context: the same image again uploads nothing.  A new one bumps ws_gen (graphs recorded on
 // the old tables are stale) and cannot be recorded.
@@ -388,21 +411,7 @@ static vw_status cwt_upload(vw_ctx* c, const CwtPlan& p, const vw_cwt_scale* sca
     T* him = reinterpret_cast<T*>(img.data() + sc_bytes + tab_bytes);
     for (int64_t i = 0; i < ntaps; ++i) him[i] = (T)taps_im[i];
   }
-  if (img != c->cwt_img) {
-    if (c->capturing) return fail(VW_ERR_STATE, "vw_cwt: new tables cannot be uploaded during a capture (run the call once first)");
-    if (c->cwt_dev_bytes < bytes) {
-      VW_HIP(hipStreamSynchronize(c->stream));
-      if (c->cwt_dev) hipFree(c->cwt_dev);
-      c->cwt_dev = nullptr; c->cwt_dev_bytes = 0; c->cwt_img.clear();
-      VW_HIP(hipMalloc(&c->cwt_dev, bytes));
-      c->cwt_dev_bytes = bytes;
-    }
-    c->cwt_img.clear();  // (not valid until the copy is enqueued)
-    VW_HIP(hipMemcpyAsync(c->cwt_dev, img.data(), bytes, hipMemcpyHostToDevice, c->stream));
-    VW_HIP(hipStreamSynchronize(c->stream));  // img is this call's
-    c->cwt_img.swap(img);
-    ++c->ws_gen;
-  }
+  VW_TRY(image_upload(c, &c->cwt_dev, &c->cwt_dev_bytes, &c->cwt_img, &img, bytes, "vw_cwt"));
   const unsigned char* base = static_cast<const unsigned char*>(c->cwt_dev);
   a->sc = reinterpret_cast<const CwtScaleDev<T>*>(base);
   a->taps_re = reinterpret_cast<const T*>(base + sc_bytes);
@@ -475,4 +484,110 @@ extern "C" vw_status vw_cwt_f32(vw_ctx* c, const float* x, int64_t B, int64_t N,
                                 int S, const double* taps_re, const double* taps_im, int64_t ntaps, int ext, int64_t wrap,
                                 unsigned flags, float* out_re, float* out_im) {
   return cwt_impl<float>(c, x, B, N, ldx, scales, S, taps_re, taps_im, ntaps, ext, wrap, flags, out_re, out_im);
+}
+
+// ------------------------------------------------------------------------------------------------
+// Inverse continuous wavelet transform (vw_icwt.hip): InverseCWT.reconstruct on coefficient planes, plan_icwt's one
+// launch (SUM) or one thread per output (DIRECT).  Timing family: "icwt".
+
+// The call's device image: [IcwtScaleDev x nsc, the caller's order][taps x ntaps], T-typed, 16-byte aligned parts,
+// in the context's slot of its own (image_upload).
+template <typename T>
+static vw_status icwt_upload(vw_ctx* c, const vw_icwt_scale* scales, int nsc, const double* taps, int64_t ntaps,
+                             IcwtArgs<T>* a) {
+  const size_t sc_bytes = align_up((size_t)nsc * sizeof(IcwtScaleDev<T>), 16);
+  const size_t tab_bytes = align_up((size_t)ntaps * sizeof(T), 16);
+  const size_t bytes = sc_bytes + tab_bytes;
+  std::vector<unsigned char> img(bytes + 1, 0);
+  img[bytes] = (unsigned char)sizeof(T);  // the layout's own parameter closes the image
+  IcwtScaleDev<T>* hs = reinterpret_cast<IcwtScaleDev<T>*>(img.data());
+  for (int i = 0; i < nsc; ++i) {
+    const vw_icwt_scale& d = scales[i];
+    IcwtScaleDev<T> e;
+    std::memset(&e, 0, sizeof(e));  // the image is compared byte for byte, padding included
+    e.tap_begin = (int)d.tap_begin; e.taps = d.taps; e.window = d.window_begin; e.plane = d.plane;
+    e.weight = (T)d.weight; e.scale = (T)d.scale;
+    std::memcpy(&hs[i], &e, sizeof(e));
+  }
+  T* ht = reinterpret_cast<T*>(img.data() + sc_bytes);
+  for (int64_t i = 0; i < ntaps; ++i) ht[i] = (T)taps[i];
+  VW_TRY(image_upload(c, &c->icwt_dev, &c->icwt_dev_bytes, &c->icwt_img, &img, bytes, "vw_icwt"));
+  const unsigned char* base = static_cast<const unsigned char*>(c->icwt_dev);
+  a->sc = reinterpret_cast<const IcwtScaleDev<T>*>(base);
+  a->taps = reinterpret_cast<const T*>(base + sc_bytes);
+  return VW_OK;
+}
+
+template <typename T>
+static vw_status icwt_impl(vw_ctx* c, const T* coef, int64_t B, int S, int64_t N, int64_t ldc,
+                           const vw_icwt_scale* scales, int nsc, const double* taps, int64_t ntaps, int form,
+                           int64_t wrap, double divisor, unsigned flags, T* out, int64_t ldo) {
+  if (!c) return fail(VW_ERR_NULL, "ctx is null");
+  if (!coef || !scales || !taps || !out) return fail(VW_ERR_NULL, "null array argument");
+  if (B <= 0) return fail(VW_ERR_EMPTY, "batch must be non-empty (B=%lld)", (long long)B);
+  if (N <= 0) return fail(VW_ERR_EMPTY, "Signal cannot be empty");
+  if (S <= 0 || nsc <= 0) return fail(VW_ERR_EMPTY, "Scales cannot be empty");
+  if (N > (1LL << 30)) return fail(VW_ERR_ARG, "signal length %lld too large", (long long)N);
+  if (ldc < N) return fail(VW_ERR_ARG, "ldc (%lld) < N (%lld)", (long long)ldc, (long long)N);
+  if (ldo < N) return fail(VW_ERR_ARG, "ldo (%lld) < N (%lld)", (long long)ldo, (long long)N);
+  if (flags & ~(unsigned)(VW_FLAG_FMA | VW_FLAG_HOST_MEMORY | VW_FLAG_SYNC))
+    return fail(VW_ERR_ARG, "vw_icwt takes FMA, HOST_MEMORY and SYNC only");
+  if (form != VW_ICWT_SUM && form != VW_ICWT_DIRECT) return fail(VW_ERR_ARG, "unknown form %d", form);
+  if (form == VW_ICWT_DIRECT && (flags & VW_FLAG_FMA))
+    return fail(VW_ERR_ARG, "VW_FLAG_FMA is not supported by VW_ICWT_DIRECT (every term ends in a division)");
+  if (form == VW_ICWT_SUM && wrap < N)
+    return fail(VW_ERR_ARG, "VW_ICWT_SUM needs wrap >= N (wrap=%lld, N=%lld)", (long long)wrap, (long long)N);
+  if (!(divisor > 0.0) || !((T)divisor > (T)0) || std::isinf((T)divisor))
+    return fail(VW_ERR_ARG, "divisor %g (must be positive and finite)", divisor);
+  if (ntaps < 1 || ntaps > (1LL << 30)) return fail(VW_ERR_ARG, "ntaps (%lld) outside 1..2^30", (long long)ntaps);
+  std::vector<int> K((size_t)nsc);
+  for (int j = 0; j < nsc; ++j) {
+    const vw_icwt_scale& d = scales[j];
+    if (d.taps < 1) return fail(VW_ERR_ARG, "scale %d has %d taps", j, (int)d.taps);
+    if (d.tap_begin < 0 || d.tap_begin > ntaps - d.taps)
+      return fail(VW_ERR_ARG, "scale %d reads taps [%lld, %lld) outside the table of %lld", j, (long long)d.tap_begin,
+                  (long long)d.tap_begin + d.taps, (long long)ntaps);
+    if (d.plane < 0 || d.plane >= S) return fail(VW_ERR_ARG, "scale %d reads plane %d outside [0, %d)", j, (int)d.plane, S);
+    if (d.window_begin > (1 << 30) || d.window_begin < -(1 << 30))
+      return fail(VW_ERR_ARG, "scale %d has window_begin %d outside +-2^30", j, (int)d.window_begin);
+    if (form == VW_ICWT_DIRECT && d.taps != 2 * N - 1)
+      return fail(VW_ERR_ARG, "scale %d has %d taps: VW_ICWT_DIRECT reads 2N - 1 = %lld", j, (int)d.taps, (long long)(2 * N - 1));
+    K[j] = d.taps;
+  }
+  IcwtCall k;
+  k.B = B; k.N = N; k.nsc = nsc; k.taps = K.data(); k.elem_bytes = (int)sizeof(T); k.flags = flags;
+  IcwtPlan p;
+  plan_icwt(k, &p);
+  if (p.error != VW_OK) return fail((vw_status)p.error, "%s", p.msg);
+
+  Staging stg(c, flags);
+  VW_TRY(stg.open());
+  IcwtArgs<T> a{};
+  VW_TRY(icwt_upload<T>(c, scales, nsc, taps, ntaps, &a));
+  a.B = B; a.N = (int)N; a.S = S; a.nsc = nsc; a.ntiles = p.ntiles; a.wrap = form == VW_ICWT_SUM ? wrap : N;
+  a.divisor = (T)divisor;
+  a.coef = coef; a.ldc = ldc; a.out = out; a.ldo = ldo;
+  if (stg.host()) {  // rows packed on the device: the host's padding is neither read nor written
+    VW_TRY(stg.in_planes(&a.coef, (size_t)B * (size_t)S, (size_t)N, (size_t)ldc));
+    VW_TRY(stg.out_planes(&a.out, (size_t)B, (size_t)N, (size_t)ldo));
+    a.ldc = N; a.ldo = N;
+  }
+  {
+    LaunchTimer lt(c, "icwt");
+    hipError_t e = form == VW_ICWT_SUM ? launch_icwt<T>(a, p.threads, p.lds, p.fma, p.grid, c->stream)
+                                       : launch_icwt_direct<T>(a, c->stream);
+    if (e != hipSuccess) return fail(VW_ERR_DEVICE, "icwt launch failed: %s", hipGetErrorString(e));
+  }
+  return stg.finish();
+}
+
+extern "C" vw_status vw_icwt_f64(vw_ctx* c, const double* coef, int64_t B, int S, int64_t N, int64_t ldc,
+                                 const vw_icwt_scale* scales, int nsc, const double* taps, int64_t ntaps, int form,
+                                 int64_t wrap, double divisor, unsigned flags, double* out, int64_t ldo) {
+  return icwt_impl<double>(c, coef, B, S, N, ldc, scales, nsc, taps, ntaps, form, wrap, divisor, flags, out, ldo);
+}
+extern "C" vw_status vw_icwt_f32(vw_ctx* c, const float* coef, int64_t B, int S, int64_t N, int64_t ldc,
+                                 const vw_icwt_scale* scales, int nsc, const double* taps, int64_t ntaps, int form,
+                                 int64_t wrap, double divisor, unsigned flags, float* out, int64_t ldo) {
+  return icwt_impl<float>(c, coef, B, S, N, ldc, scales, nsc, taps, ntaps, form, wrap, divisor, flags, out, ldo);
 }

@@ -305,6 +305,7 @@ extern "C" vw_status vw_ctx_destroy(vw_ctx* c) {
   if (c->med) hipFree(c->med);
   if (c->nf) hipFree(c->nf);
   if (c->cwt_dev) hipFree(c->cwt_dev);
+  if (c->icwt_dev) hipFree(c->icwt_dev);
   for (auto& b : c->stage) hipFree(b.first);
   if (c->bad) hipFree(c->bad);
   if (c->own_stream) hipStreamDestroy(c->stream);

@@ -14,50 +14,13 @@
 // the staged tile: one chunk read (two 16-byte LDS reads) per NV taps feeds NV * NV multiplies, 2 NV * NV with a
 // complex table.  The taps are wave-uniform and read through scalar loads.  Each output keeps its own k order,
 // so without FMA the sums are the reference's bit for bit.
-#include "vw_launch_k.h"
+#include "vw_cwt_dev.h"
 
 #ifndef VW_T
 #error "compile with -DVW_T=double or -DVW_T=float"
 #endif
 
 namespace vw {
-
-// CWTTransform.getBoundaryValue (:354-396) for every index, the in-range read (:147-149) included.
-template <typename T>
-__device__ __forceinline__ T cwt_ext(const T* __restrict__ x, long long i, int N, int ext, long long M) {
-  if (ext == kCwtWrapZero) {
-    long long m = i % M;
-    if (m < 0) m += M;
-    return m < N ? x[m] : T(0);
-  }
-  if (i >= 0 && i < N) return x[i];
-  switch (ext) {
-    case kCwtReflect: {
-      long long r = i < 0 ? -i : 2LL * N - i - 2;
-      if (i < 0 && r >= N) r = N - 1;
-      if (i >= N && r < 0) r = 0;
-      return x[r];
-    }
-    case kCwtSymmetric: {
-      long long r = i < 0 ? -i - 1 : 2LL * N - i - 1;
-      if (i < 0 && r >= N) r = N - 1;
-      if (i >= N && r < 0) r = 0;
-      return x[r];
-    }
-    case kCwtPeriodic: return x[((i % N) + N) % N];
-    default: return T(0);
-  }
-}
-
-// LDS element of staged element e: chunk q = e / NV as two 16-byte halves, half h of every chunk in plane h, so the
-// 64 lanes of a wave read 64 consecutive 16-byte slots of one plane (no bank conflict; adjacent chunks in one
-// array would put lanes l and l + 8 of a ds_read_b128 group on the same banks).
-template <int NV>
-__device__ __forceinline__ int cwt_slot(int e, int chunks) {
-  constexpr int V = NV / 2;
-  const int q = e / NV, c = e % NV;
-  return ((c / V) * chunks + q) * V + c % V;
-}
 
 template <typename T, bool CPLX, bool FMA>
 __global__ void __launch_bounds__(kCwtThreads)

@@ -92,6 +92,9 @@ struct vw_ctx {
   void* cwt_dev = nullptr;     // vw_cwt_*: the scale descriptors and tap tables of the last call, on the device
   size_t cwt_dev_bytes = 0;
   std::vector<unsigned char> cwt_img;  // ... and the host image they were copied from (a call with the same one uploads nothing)
+  void* icwt_dev = nullptr;    // vw_icwt_*: the same for the inverse, in a slot of its own (alternating calls keep both images)
+  size_t icwt_dev_bytes = 0;
+  std::vector<unsigned char> icwt_img;
 };
 
 struct vw_graph {

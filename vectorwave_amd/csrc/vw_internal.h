@@ -390,6 +390,42 @@ struct CwtArgs {
   long long wrap;              // M of kCwtWrapZero
 };
 
+// Inverse continuous wavelet transform (vw_icwt.hip): InverseCWT.reconstruct (cwt/InverseCWT.java) on coefficient
+// planes [B][S][ldc] into rows [B][ldo].
+//   kIcwtSum     out[b][tau] = (sum_j weight_j * (sum_k w_j[k] * z_{b,plane_j}[(tau + o_j + k) mod wrap])) / divisor, z zero
+//                on [N, wrap): what reconstructInternalRealFFT (:225-270) evaluates by FFT.  One accumulator per
+//                descriptor from +0.0, k ascending; one outer accumulator from +0.0, j ascending (k_icwt).
+//   kIcwtDirect  reconstructInternalRealDirect's loops (:283-311): one accumulator over j and b ascending of
+//                ((c * w_j[t - b + N - 1]) * weight_j) / scale_j, terms with |c| < 1e-10 skipped (k_icwt_direct).
+enum IcwtForm : int { kIcwtSum = 0, kIcwtDirect = 1 };
+constexpr int kIcwtDirectThreads = 64;  // a k_icwt_direct workgroup: one thread per output
+// One descriptor as the kernels read it (device memory, the caller's order), weight and scale rounded to T once.
+template <typename T>
+struct IcwtScaleDev {
+  int tap_begin;   // first tap in taps
+  int taps;        // K_j
+  int window;      // o_j
+  int plane;       // the coefficient plane it reads
+  T weight;
+  T scale;         // kIcwtDirect only
+};
+template <typename T>
+struct IcwtArgs {
+  const T* coef;               // [B][S][ldc]
+  long long ldc;
+  T* out;                      // [B][ldo]
+  long long ldo;
+  const T* taps;               // device table, rounded to T once on the host
+  const IcwtScaleDev<T>* sc;   // the call's descriptors
+  long long B;
+  int N;
+  int S;                       // planes per row
+  int nsc;                     // descriptors
+  int ntiles;                  // ceil(N / (threads * NV)), kIcwtSum
+  long long wrap;              // M, kIcwtSum
+  T divisor;
+};
+
 // Register-blocked kernels (vw_blk.h k_forward_blk / k_inverse_blk, and k_inverse_multi's blocked levels):
 // the padded LDS layout of a level with vector stride m and nv outputs per thread, the one rule for the
 // planner (buffer sizes) and the kernels (addresses).  NV = 4: one pad vector per 4 (m <= 4), two per 8

@@ -80,6 +80,13 @@ hipError_t launch_mra(const MraArgs<T>& a, int threads, int lds_bytes, bool fma,
 template <typename T>
 hipError_t launch_cwt(const CwtArgs<T>& a, int threads, int lds_bytes, bool cplx, bool fma, int grid, hipStream_t st);
 
+// Inverse continuous wavelet transform (vw_icwt.hip): the SUM form by plan_icwt's shape, the DIRECT form one
+// thread per output
+template <typename T>
+hipError_t launch_icwt(const IcwtArgs<T>& a, int threads, int lds_bytes, bool fma, int grid, hipStream_t st);
+template <typename T>
+hipError_t launch_icwt_direct(const IcwtArgs<T>& a, hipStream_t st);
+
 // Streaming history, thresholds, statistics and utilities (vw_misc.hip)
 template <typename T>
 hipError_t launch_history_update(const T* level_in, long long ld_in, const T* old_hist, T* new_hist,

@@ -1189,6 +1189,28 @@ void plan_cwt(const CwtCall& c, CwtPlan* p) {
   }
 }
 
+void plan_icwt(const IcwtCall& c, IcwtPlan* p) {
+  p->fma = (c.flags & VW_FLAG_FMA) != 0;
+  const int nv = kCwtChunkBytes / c.elem_bytes;
+  const int64_t want = ((c.N + nv - 1) / nv + 63) / 64 * 64;  // whole waves covering the row, as plan_cwt
+  const int threads = (int)std::min<int64_t>(want, kCwtThreads);
+  const int tile = threads * nv;
+  p->threads = threads; p->nv = nv; p->tile = tile;
+  p->ntiles = (int)((c.N + tile - 1) / tile);
+  for (int j = 0; j < c.nsc; ++j) {
+    const int K = c.taps[j];
+    if (K > kCwtMaxTaps) {
+      p->error = VW_ERR_UNSUPPORTED;
+      snprintf(p->msg, sizeof(p->msg), "scale %d has %d taps: more than the %d a workgroup stages", j, K, kCwtMaxTaps);
+      return;
+    }
+    p->max_taps = std::max(p->max_taps, K);
+  }
+  p->chunks = cwt_chunks(threads, p->max_taps, nv);
+  p->lds = p->chunks * kCwtChunkBytes;
+  p->grid = (int)std::min<int64_t>((int64_t)p->ntiles * c.B, kCwtMaxGrid);
+}
+
 template <typename T>
 void plan_forward(const Tuning& tu, const FwdCall<T>& c, FwdPlan<T>* p) {
   const int Lmax = std::max(c.L, hi_taps(c)), taps = listed_taps(tu, Lmax, c.L != hi_taps(c));

@@ -252,6 +252,29 @@ struct CwtPlan {
 };
 void plan_cwt(const CwtCall& c, CwtPlan* p);
 
+// vw_icwt_* in the SUM form (vw_icwt.hip k_icwt): one workgroup per (row, time tile) loops over every descriptor, so
+// the call has one launch.  Threads, NV and the tile as plan_cwt; the staged chunks and the LDS are those of the
+// call's longest table (cwt_chunks), every shorter one stages into the same bytes.  grid = min(B * ntiles,
+// kCwtMaxGrid), the kernel strides over the rest.  A descriptor with K > kCwtMaxTaps is refused: error
+// VW_ERR_UNSUPPORTED, `msg` names it, nothing else of the plan is valid.
+struct IcwtCall {
+  int64_t B = 0, N = 0;
+  int nsc = 0;
+  const int* taps = nullptr;  // K_j per descriptor (>= 1, checked by the caller)
+  int elem_bytes = 8;
+  unsigned flags = 0;
+};
+struct IcwtPlan {
+  int error = VW_OK;
+  char msg[96] = "";
+  bool fma = false;
+  int threads = 0, nv = 0, tile = 0, ntiles = 0;
+  int max_taps = 0;     // the longest table
+  int chunks = 0, lds = 0;
+  int grid = 0;
+};
+void plan_icwt(const IcwtCall& c, IcwtPlan* p);
+
 // Banks with two lengths (Lhi != 0 and != L; the _bi_ entry points) run the same kernels on the PADDED ROUTE: the
 // shorter filter is zero-extended to args.taps = max(L, Lhi), or one tap further where only that count has
 // tap-unrolled kernels (VW_BI_LISTED, vw_plan.cpp listed_taps) -- for finite data a trailing 0 * x adds +-0 to a

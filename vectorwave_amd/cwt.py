@@ -1,6 +1,7 @@
-"""Continuous wavelet transform: host-side mirror of the reference's ``cwt`` package over vw_cwt_*.
+"""Continuous wavelet transform: host-side mirror of the reference's ``cwt`` package over vw_cwt_* / vw_icwt_*.
 
   CWTTransform.analyze, CWTConfig, CWTResult, ScaleSpace          (cwt/)
+  InverseCWT.reconstruct / reconstructBand / reconstructFrequencyBand  (cwt/)
   MorletWavelet, RickerWavelet                                    (cwt/)
   PaulWavelet, DOGWavelet                                         (cwt/finance/)
 
@@ -20,13 +21,23 @@ branch as ``CWTTransform.analyze`` (cwt/CWTTransform.java:71-79) does:
 can differ from the Java one in the last bits; the Java facade (AmdCWTTransform) builds its tables with the
 wavelet's own ``psi``, so the drop-in is unaffected.  Given a table, the sums are the reference's bit for bit.
 
-Not here: analyzeComplex (its direct form divides every term, :523-541, so it is no table correlation), the
-inverse transforms, the adaptive scale selectors, the remaining wavelet classes and the cwt/finance analyzers.
+The inverse (``InverseCWT``, cwt/InverseCWT.java) always reads the real plane and picks its route as :213 does:
+
+  N >= 128   reconstructInternalRealFFT (:225-270): the weighted sum of circular convolutions over M = nextPowerOfTwo(N)
+             that the reference's FFTs evaluate, r[i] = (sum_s wt_s sum_d g_s(d) z_s[(i - d) mod M]) / C_psi with
+             g_s(d) = psi(d / a_s) / sqrt(a_s), d in (-M/2, M/2].  The GPU evaluates that sum in a fixed order; a table
+             is cut at its outermost non-zero entries, which changes no finite result by a bit.
+  N < 128    reconstructInternalRealDirect (:275-314): the reference's loops, term by term.
+
+Not here: analyzeComplex (its direct form divides every term, :523-541, so it is no table correlation),
+MODWTBasedInverseCWT, reconstruction from complex coefficients (the reference has none: its ComplexMatrix overload is
+dead code), the adaptive scale selectors, the remaining wavelet classes and the cwt/finance analyzers.
 """
 from __future__ import annotations
 
 import enum
 import math
+from decimal import Decimal
 from dataclasses import dataclass
 from typing import List, Optional, Sequence, Tuple
 
@@ -34,7 +45,7 @@ import numpy as np
 
 from . import _native as nat
 from .engine import Engine
-from .errors import InvalidArgumentException
+from .errors import InvalidArgumentException, InvalidConfigurationException
 
 try:
     import torch
@@ -509,3 +520,242 @@ class CWTTransform:
         t = self.tables(scales, int(shape[-1]))
         re, im = eng.cwt(signal, t.scales, t.taps_re, t.taps_im, t.ext, t.wrap, nat.FLAG_FMA if self.fma else 0)
         return CWTResult(re, im, scales, self.wavelet)
+
+
+# ---- inverse ---------------------------------------------------------------------------------------------------
+ICWT_FFT_MIN_LENGTH = 128   # InverseCWT.java:213
+
+
+def _jd(x: float) -> str:
+    """Double.toString for the values the reference's messages print."""
+    x = float(x)
+    if x != x:
+        return "NaN"
+    if x in (math.inf, -math.inf):
+        return "Infinity" if x > 0 else "-Infinity"
+    if x == 0 or 1e-3 <= abs(x) < 1e7:
+        return repr(x)
+    sign, digits, exp = Decimal(repr(x)).as_tuple()   # the shortest digits that round-trip, as Java prints
+    digits = "".join(map(str, digits)).rstrip("0") or "0"
+    e = len(Decimal(repr(x)).as_tuple().digits) - 1 + exp
+    m = ("-" if sign else "") + digits[0] + "." + (digits[1:] or "0")
+    return f"{m}E{e}"
+
+
+def log_scale_weights(scales: Sequence[float], start: int, end: int) -> List[float]:
+    """InverseCWT.calculateLogScaleWeights (:411-453)."""
+    n = end - start
+    if n <= 0:
+        return []
+    if start < 0 or end > len(scales):
+        raise InvalidArgumentException(
+            f"Scale indices out of bounds: start={start}, end={end}, scales.length={len(scales)}")
+    for i in range(start, end):
+        if scales[i] <= 0:
+            raise InvalidArgumentException("Scale values must be positive for logarithmic integration. "
+                                           f"Found non-positive scale at index {i}: {_jd(scales[i])}")
+    if n == 1:
+        return [float(scales[start])]
+    weights = [0.0] * n
+    for i in range(n):
+        if i == 0:
+            weights[i] = math.log(scales[start + 1] / scales[start]) / 2.0
+        elif i == n - 1:
+            weights[i] = math.log(scales[start + i] / scales[start + i - 1]) / 2.0
+        else:
+            weights[i] = math.log(scales[start + i + 1] / scales[start + i - 1]) / 2.0
+    return weights
+
+
+def admissibility_numerical(wavelet: ContinuousWavelet) -> float:
+    """InverseCWT.calculateAdmissibilityNumerical / waveletFourierTransform (:490-538): every frequency's sums run
+    over t in the reference's order (one numpy operation per t over all frequencies), the outer sum in its order."""
+    nPoints, maxFreq = 10000, 100.0
+    freqs = np.zeros(nPoints)
+    for i in range(1, nPoints):
+        freqs[i] = maxFreq * math.pow(10.0, -4.0 + 4.0 * i / (nPoints - 1))
+    omega = freqs[1:nPoints - 1]
+    nT, tMax = 1000, 20.0
+    dt = 2.0 * tMax / nT
+    realSum = np.zeros_like(omega)
+    imagSum = np.zeros_like(omega)
+    for i in range(nT):
+        t = -tMax + i * dt
+        psi = wavelet.psi(t)
+        arg = -omega * t
+        realSum = realSum + psi * np.cos(arg) * dt
+        imagSum = imagSum + psi * np.sin(arg) * dt
+    psiHat = np.sqrt(realSum * realSum + imagSum * imagSum)
+    integrand = psiHat * psiHat / omega
+    total = 0.0
+    for i in range(1, nPoints - 1):
+        dOmega = (freqs[i + 1] - freqs[i - 1]) / 2.0
+        total += float(integrand[i - 1]) * dOmega
+    return float(2.0 * math.pi * total)
+
+
+def admissibility_constant(wavelet: ContinuousWavelet) -> float:
+    """InverseCWT.calculateAdmissibilityConstant (:462-485): by name, else numerically (cached on the wavelet)."""
+    name = wavelet.name().lower()
+    if "morlet" in name or "morl" in name:
+        return math.pi
+    if "mexh" in name or "dog2" in name:
+        return math.pi / math.sqrt(2.0)
+    if "dog" in name:
+        return math.pi
+    if "paul" in name:
+        return 2.0 * math.pi
+    if "shannon" in name:
+        return math.pi
+    cached = getattr(wavelet, "_admissibility_numerical", None)
+    if cached is None:
+        cached = admissibility_numerical(wavelet)
+        try:
+            wavelet._admissibility_numerical = cached
+        except AttributeError:  # pragma: no cover  (a wavelet class with __slots__)
+            pass
+    return cached
+
+
+@dataclass
+class ICWTTables:
+    """What one vw_icwt_* call takes, for a wavelet, the scales [start, end) of a result and a row length."""
+    form: int                                               # nat.ICWT_SUM or nat.ICWT_DIRECT
+    scales: List[Tuple[int, int, int, int, float, float]]   # (tap_begin, taps, window_begin, plane, weight, scale)
+    taps: np.ndarray                                        # float64, flat
+    wrap: int                                               # M of ICWT_SUM (0 otherwise)
+    divisor: float                                          # C_psi
+
+
+def inverse_kernel_row(wavelet: ContinuousWavelet, scale: float, M: int) -> Tuple[int, List[float]]:
+    """createWaveletFFT's time-domain table (:561-586) as g(d) = psi(d / scale) / sqrt(scale) over d in (-M/2, M/2]
+    (index i <= M/2: d = i, else d = i - M).  -> (d_min, [g(d_min) .. g(M/2)])."""
+    d_min = -(M // 2) + 1 if M > 1 else 0
+    sqrtScale = math.sqrt(scale)
+    return d_min, [wavelet.psi(d / scale) / sqrtScale for d in range(d_min, M // 2 + 1)]
+
+
+def build_inverse_tables(wavelet: ContinuousWavelet, scales: Sequence[float], N: int, start: int, end: int,
+                         trim: bool = True) -> ICWTTables:
+    """The table and descriptors of InverseCWT.reconstructInternalReal(planes, scales, N, start, end): the route as
+    :213.  trim=False keeps every entry of a SUM table (tests: trimming changes no bit)."""
+    weights = log_scale_weights(scales, start, end)
+    c_psi = admissibility_constant(wavelet)
+    desc, taps = [], []
+    if N >= ICWT_FFT_MIN_LENGTH:
+        M = next_power_of_two(N)
+        for j in range(start, end):
+            a = scales[j]
+            d_min, g = inverse_kernel_row(wavelet, a, M)
+            lo, hi = 0, len(g) - 1
+            if trim:   # an entry that is exactly 0.0 adds nothing to a finite sum
+                while hi > lo and g[hi] == 0.0:
+                    hi -= 1
+                while lo < hi and g[lo] == 0.0:
+                    lo += 1
+            d_max = d_min + hi
+            begin = len(taps)
+            taps.extend(g[i] for i in range(hi, lo - 1, -1))   # w[k] = g(d_max - k)
+            desc.append((begin, hi - lo + 1, -d_max, j, weights[j - start] / a, a))
+        return ICWTTables(nat.ICWT_SUM, desc, np.asarray(taps, dtype=np.float64), M, c_psi)
+    for j in range(start, end):   # reconstructionKernel (:359-374): (1.0 / sqrt(a)) * psi((t - b) / a)
+        a = scales[j]
+        scaleFactor = 1.0 / math.sqrt(a)
+        begin = len(taps)
+        taps.extend(scaleFactor * wavelet.psi(d / a) for d in range(-(N - 1), N))
+        desc.append((begin, 2 * N - 1, 0, j, weights[j - start], a))
+    return ICWTTables(nat.ICWT_DIRECT, desc, np.asarray(taps, dtype=np.float64), 0, c_psi)
+
+
+class InverseCWT:
+    """cwt/InverseCWT.java over a CWTResult holding planes [S, N] (one signal) or [B, S, N] (a batch), numpy (host
+    memory) or CUDA tensors (device memory), float64 or float32 -> [N] / [B, N] in the same memory.  fma=True: one
+    fma per term of the N >= 128 route instead of separate multiplies and adds (the N < 128 route divides every term:
+    the flag is dropped there)."""
+
+    def __init__(self, wavelet: ContinuousWavelet, fma: bool = False, engine: Optional[Engine] = None):
+        if wavelet is None:
+            raise InvalidArgumentException("Wavelet cannot be null")
+        self.wavelet = wavelet
+        self.admissibilityConstant = admissibility_constant(wavelet)
+        if self.admissibilityConstant <= 0 or math.isinf(self.admissibilityConstant):
+            raise InvalidConfigurationException(
+                "Wavelet does not satisfy admissibility condition: C_ψ = " + _jd(self.admissibilityConstant))
+        self.fma = bool(fma)
+        self._engine = engine
+        self._tables = {}
+
+    def getAdmissibilityConstant(self) -> float:
+        return self.admissibilityConstant
+
+    def isAdmissible(self) -> bool:
+        return self.admissibilityConstant > 0 and self.admissibilityConstant < math.inf
+
+    def tables(self, scales: Sequence[float], N: int, start: int, end: int) -> ICWTTables:
+        key = (tuple(scales), N, start, end)
+        t = self._tables.get(key)
+        if t is None:
+            self._tables.clear()   # one shape at a time, as CWTTransform.tables
+            t = self._tables[key] = build_inverse_tables(self.wavelet, scales, N, start, end)
+        return t
+
+    def reconstruct(self, cwtResult: CWTResult):
+        if cwtResult is None:
+            raise InvalidArgumentException("CWT result cannot be null")
+        scales = cwtResult.getScales()
+        if scales is None or len(scales) == 0:
+            raise InvalidArgumentException("CWT result has no scales")
+        coeffs = cwtResult.getCoefficients()
+        signalLength = cwtResult.getNumSamples() if coeffs is not None else 0
+        if coeffs is not None and signalLength <= 0:
+            raise InvalidArgumentException(f"Invalid signal length: {signalLength}")
+        if coeffs is None or coeffs.shape[-2] == 0:
+            raise InvalidArgumentException("CWT result has no coefficients")
+        return self._reconstruct(coeffs, scales, signalLength, 0, len(scales))
+
+    def reconstructBand(self, cwtResult: CWTResult, minScale: float, maxScale: float):
+        if cwtResult is None:
+            raise InvalidArgumentException("CWT result cannot be null")
+        if minScale <= 0 or maxScale <= minScale:
+            raise InvalidArgumentException(f"Invalid scale range: minScale={_jd(minScale)}, maxScale={_jd(maxScale)}")
+        scales = cwtResult.getScales()
+        signalLength = cwtResult.getNumSamples()
+        startIdx = endIdx = -1
+        for i, s in enumerate(scales):
+            if startIdx == -1 and s >= minScale:
+                startIdx = i
+            if s > maxScale:
+                endIdx = i
+                break
+        if startIdx == -1:
+            startIdx = 0
+        if endIdx == -1:
+            endIdx = len(scales)
+        coeffs = cwtResult.getCoefficients()
+        if startIdx >= endIdx:   # no scale in the requested range: the zero signal (:164-167)
+            shape = tuple(coeffs.shape[:-2]) + (signalLength,)
+            if _is_tensor(coeffs):
+                return torch.zeros(shape, dtype=coeffs.dtype, device=coeffs.device)
+            return np.zeros(shape, dtype=np.float32 if coeffs.dtype == np.float32 else np.float64)
+        return self._reconstruct(coeffs, scales, signalLength, startIdx, endIdx)
+
+    def reconstructFrequencyBand(self, cwtResult: CWTResult, samplingRate: float, minFreq: float, maxFreq: float):
+        if samplingRate <= 0:
+            raise InvalidArgumentException("Sampling rate must be positive")
+        if minFreq < 0 or maxFreq <= minFreq or maxFreq > samplingRate / 2:
+            raise InvalidArgumentException(f"Invalid frequency range: minFreq={_jd(minFreq)}, maxFreq={_jd(maxFreq)}")
+        centerFreq = self.wavelet.centerFrequency()
+        maxScale = centerFreq * samplingRate / minFreq if minFreq != 0 else math.copysign(math.inf, centerFreq * samplingRate)
+        minScale = centerFreq * samplingRate / maxFreq
+        return self.reconstructBand(cwtResult, minScale, maxScale)
+
+    def _reconstruct(self, coeffs, scales, N: int, start: int, end: int):
+        if len(coeffs.shape) not in (2, 3):
+            raise InvalidArgumentException("Coefficients must be [S, N] or [B, S, N]")
+        eng = self._engine
+        if eng is None:
+            dev = coeffs.device.index if (_is_tensor(coeffs) and coeffs.is_cuda) else None
+            eng = Engine.get(dev)
+        t = self.tables(scales, N, start, end)
+        flags = nat.FLAG_FMA if (self.fma and t.form == nat.ICWT_SUM) else 0
+        return eng.icwt(coeffs, t.scales, t.taps, t.form, t.wrap, t.divisor, flags)

@@ -445,6 +445,38 @@ class Engine:
                   self._ptr(ore, dev), self._ptr(oim, dev)))
         return ore, oim
 
+    # -- inverse continuous wavelet transform (vw_icwt_*) -------------------------------------------
+    def icwt(self, coef, scales, taps, form: int, wrap: int, divisor: float, flags: int = 0,
+             N: Optional[int] = None, out=None):
+        """Coefficient planes coef [S, ld] or [B, S, ld] (N: the row length when the rows carry padding, ld > N) ->
+        [N] / [B, N].  scales: a sequence of (tap_begin, taps, window_begin, plane, weight, scale) into the flat
+        float64 table ``taps``.  form nat.ICWT_SUM: out = (sum_j weight_j (sum_k w_j[k] z_plane_j[(tau + o_j + k) mod
+        wrap])) / divisor; nat.ICWT_DIRECT: InverseCWT's direct loops.  out: an array [B, ldo] (ldo >= N) in coef's
+        memory to write instead of a new one."""
+        ca, dev, cp, f32 = self._prep(coef)
+        if ca.ndim not in (2, 3):
+            raise ValueError("coef must be [S, N] or [B, S, N]")
+        one = ca.ndim == 2
+        B, S, ld = (1,) + tuple(ca.shape) if one else tuple(ca.shape)
+        N = ld if N is None else int(N)
+        nsc = len(scales)
+        desc = (nat.IcwtScale * max(nsc, 1))()
+        for i, (t0, k, o, pl, wt, sc) in enumerate(scales):
+            desc[i] = nat.IcwtScale(int(t0), int(k), int(o), int(pl), float(wt), float(sc))
+        tab = np.ascontiguousarray(taps, dtype=np.float64)
+        if out is None:
+            res = self._empty(ca, dev, (N,) if one else (B, N))
+            ldo = N
+        else:
+            res, odev, _, of32 = self._prep(out)
+            if res is not out or odev != dev or of32 != f32:
+                raise ValueError("out must be a contiguous array of coef's element type, in the same memory")
+            ldo = int(res.shape[-1])
+        fn = self.lib.vw_icwt_f32 if f32 else self.lib.vw_icwt_f64
+        _check(fn(self.ctx, cp, B, S, N, ld, desc, nsc, tab.ctypes.data_as(ctypes.POINTER(c_double)), tab.size,
+                  int(form), int(wrap), float(divisor), self._flags(flags, dev), self._ptr(res, dev), ldo))
+        return res
+
     def transpose(self, a, rows: int, cols: int):
         """out[c][r] = a[r][c] (a: rows*cols elements, any shape) -> flat [cols*rows] array."""
         aa, dev, ap, f32 = self._prep(a)

@@ -47,6 +47,10 @@ class InvalidStateException(WaveletTransformException):
     pass
 
 
+class InvalidConfigurationException(WaveletTransformException):
+    """core/exception/InvalidConfigurationException.java (InverseCWT: a wavelet that is not admissible)."""
+
+
 class DeviceError(RuntimeError):
     """HIP runtime failure inside the engine (VW_ERR_DEVICE)."""
 
